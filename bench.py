@@ -26,6 +26,9 @@ Prints ONE JSON line on rank 0 (contract of the driver) carrying
   secondary       : BASELINE configs[1] (SpUNet-v1m1, 8 x 100000 voxels) measured in the same process
   cpu_baseline    : the CPU oracle (oracle/ptv3_model.py, port of the reference model) timed on this
                     box's host cores on a bounded sample (rank 0, N=1 only)
+
+--dump-outputs DIR writes what the last timed step computed (loss, logits, gradients, updated parameters; fixed seeded
+samples of the large ones) as DIR/*.npy, so that two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -78,6 +81,8 @@ def parse(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="launcher / DP plumbing check without a GPU: gloo backend, CPU tensors, a small torch model "
                          "(tests/test_dp_gloo.py); never a benchmark result")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -381,6 +386,51 @@ def make_step(step_model, opt, batch, amp: str, loss_of, device):
     return step
 
 
+DUMP_ROWS = 1 << 16       # logit rows kept by --dump-outputs
+DUMP_ELEMS = 1 << 20      # gradient / parameter elements kept by --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _seeded_subset(n: int, k: int, seed: int) -> torch.Tensor:
+    """k of range(n) in ascending order, the same for every run and build (all of them when n <= k)"""
+    if n <= k:
+        return torch.arange(n)
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def dump_outputs(out_dir: str, loss, logits, model) -> dict:
+    """What the last timed step handed its caller, as float32 / float64 .npy files (a fixed sample where the full array is large):
+      loss.npy          ()                      the step's loss (float64)
+      logits.npy        (rows, classes)         the seg head's output, a seeded sample of DUMP_ROWS rows (float32)
+      grad_norm.npy     (n_params,)             L2 norm of every parameter's gradient, model.parameters() order (float64)
+      grad_sample.npy   (DUMP_ELEMS,)           a seeded sample of all gradients, flattened and concatenated in that order (float32)
+      param_sample.npy  (DUMP_ELEMS,)           the same elements of the parameters after the optimizer step (float32)
+    Returns {name: shape}."""
+    import numpy as np
+
+    params = list(model.parameters())
+    grads = [torch.zeros_like(p) if p.grad is None else p.grad for p in params]
+    flat_g = torch.cat([g.detach().reshape(-1).float() for g in grads])
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    pick = _seeded_subset(flat_p.numel(), DUMP_ELEMS, 1).to(flat_p.device)
+    logits = logits.detach().reshape(logits.shape[0], -1)
+    rows = _seeded_subset(logits.shape[0], DUMP_ROWS, 2).to(logits.device)
+    arrays = {
+        "loss": np.asarray(float(loss.detach()), dtype=np.float64),
+        "logits": logits[rows].float().cpu().numpy(),
+        "grad_norm": torch.stack([g.detach().double().norm() for g in grads]).cpu().numpy(),
+        "grad_sample": flat_g[pick].cpu().numpy(),
+        "param_sample": flat_p[pick].cpu().numpy(),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def fp16_recipe_in_a_child(args):
     """The same PT-v3m1 step under the reference's own mixed-precision recipe -- fp16 autocast + torch.amp.GradScaler
     (configs/_base_/default_runtime.py:19, engines/train.py:203-231) -- measured by a CHILD process running this file with
@@ -481,8 +531,24 @@ def build_stub(args, device, rank):
     return Wrap(model), opt, batch, (lambda logits: torch.nn.functional.cross_entropy(logits.float(), seg))
 
 
+def use_prebuilt_library_if_read_only():
+    """The package loads libptcore.so through build(), and builds made before build() skipped its lock when nothing is stale
+    open a lock file in the build directory on that first use.  A built tree that belongs to another user (a second build
+    compared with this one through --dump-outputs) cannot be written here, so where this user could not take that lock the
+    benchmark runs the library that build() made as it is, the path build() takes on a box without hipcc (HIPCC="" names no
+    compiler; the ranks and the child process inherit it)."""
+    variant = os.environ.get("PTC_LIB_VARIANT", "")
+    pkg = os.path.join(ROOT, "pointcept_amd")
+    build_dir = os.path.join(pkg, "csrc", "build" + ("_" + variant if variant else ""))
+    lock = os.path.join(build_dir, ".lock")
+    target = lock if os.path.exists(lock) else build_dir if os.path.isdir(build_dir) else pkg
+    if os.path.exists(os.path.join(pkg, f"libptcore_{variant}.so" if variant else "libptcore.so")) and not os.access(target, os.W_OK):
+        os.environ["HIPCC"] = ""
+
+
 def main():
     args = parse()
+    use_prebuilt_library_if_read_only()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
     from pointcept_amd import dp
@@ -547,8 +613,17 @@ def main():
     step_model = dp.wrap_ddp(model, device)   # identity at world 1
     torch.manual_seed(100 + rank)  # order shuffles / DropPath differ per rank, as in training
     step = make_step(step_model, opt, batch, amp, loss_of, device)
+    if args.dump_outputs:
+        # the logits of the last step: the seg head's output (DefaultSegmentorV2), the model's own output otherwise (SpUNet, stub)
+        seen = {}
+        hook = getattr(model, "seg_head", model).register_forward_hook(lambda mod, inp, o: seen.__setitem__("logits", o))
     dt, loss = timed_steps(step, args.steps, args.warmup, device)
     last_loss = float(loss.detach())
+    dumped = None
+    if args.dump_outputs:
+        hook.remove()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, loss, seen.pop("logits"), model)
     # multi-GPU diagnostics (outside the timed region): every rank's own step time, and the same K steps WITHOUT the gradient exchange
     # (DDP.no_sync) -- the difference is the all-reduce time the overlap with backward did not hide
     per_rank_ms, ms_no_sync = None, None
@@ -587,6 +662,8 @@ def main():
             "config": {"workload": workload, "global_batch": args.batch * world, "parallelism": f"dp{world}", "params": n_params,
                        "amp": ("fp16 autocast + GradScaler" if amp == "fp16" else "bf16 autocast"), "final_loss": round(last_loss, 4)},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if per_rank_ms is not None:
             out["per_rank_ms_per_step"] = per_rank_ms
             out["cpu_affinity_rank0"] = affinity

@@ -129,6 +129,8 @@ def build(force: bool = False, verbose: bool = False, variant: str = "") -> str:
         if os.path.exists(LIB):
             return LIB  # GPU box without a compiler: use the prebuilt in-tree library
         raise RuntimeError(f"hipcc not found at {HIPCC} and no prebuilt {LIB}")
+    if not force and os.path.exists(LIB) and not _plan(False, variant, BUILD, HIP_FLAGS)[1]:
+        return LIB  # up to date: no lock taken, nothing written (the built tree may belong to another user and be read-only)
     os.makedirs(BUILD, exist_ok=True)
     # one builder at a time: the ranks of a multi-GPU job all pass through here (lib() -> build()); if the snapshot's
     # mtimes ever asked for a rebuild, N concurrent hipcc runs would write the same objects.  The others wait, then find
@@ -143,7 +145,8 @@ def build(force: bool = False, verbose: bool = False, variant: str = "") -> str:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(force: bool, verbose: bool, variant: str, LIB: str, BUILD: str, HIP_FLAGS: list) -> str:
+def _plan(force: bool, variant: str, BUILD: str, HIP_FLAGS: list) -> tuple:
+    """(objects the library links, compile commands still to run)"""
     hdrs = _headers()
     jobs = []
     objs = []
@@ -165,6 +168,11 @@ def _build_locked(force: bool, verbose: bool, variant: str, LIB: str, BUILD: str
                 abi = f"{zlib.crc32(open(os.path.join(HERE, '..', 'include', 'ptcore.h'), 'rb').read()) & 0xffffffff:08x}"
                 cmd = [HIPCC, "-O2", "-std=c++17", "-fPIC", f'-DPTC_ABI_HASH="{abi}"', "-x", "c++", "-c", sp, "-o", op]
             jobs.append(cmd)
+    return objs, jobs
+
+
+def _build_locked(force: bool, verbose: bool, variant: str, LIB: str, BUILD: str, HIP_FLAGS: list) -> str:
+    objs, jobs = _plan(force, variant, BUILD, HIP_FLAGS)
     if jobs:
         if verbose:
             print(f"[ptcore.build] compiling {len(jobs)} file(s) for {ARCH}")

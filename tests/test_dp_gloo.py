@@ -279,6 +279,50 @@ def test_bench_self_launch_gloo_stub():
     assert aff["pinned"] == (len(os.sched_getaffinity(0)) >= 1) and aff["cores"] >= 1 and 1 <= aff["threads"] <= 8
 
 
+def test_bench_dump_outputs_stub(tmp_path):
+    """--dump-outputs DIR: after the timed steps, the last step's loss, logits, gradients and updated parameters as float32 / float64
+    .npy files under 64 MB; two runs with the same arguments write the same arrays, a different step count different ones."""
+    import json
+
+    import numpy as np
+
+    dumps = {}
+    for tag, steps in (("a", "2"), ("b", "2"), ("c", "3")):
+        r = _run_bench("--gpus", "1", "--steps", steps, "--warmup", "1", "--batch", "2", "--stub", "--dump-outputs", str(tmp_path / tag))
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == int(steps) and out["dumped_outputs"]["dir"] == str(tmp_path / tag)
+        dumps[tag] = {f.stem: np.load(f) for f in sorted((tmp_path / tag).glob("*.npy"))}
+        assert set(dumps[tag]) == {"loss", "logits", "grad_norm", "grad_sample", "param_sample"}
+        assert {k: list(a.shape) for k, a in dumps[tag].items()} == out["dumped_outputs"]["arrays"]
+        assert all(a.dtype in (np.float32, np.float64) for a in dumps[tag].values())
+        assert sum(a.nbytes for a in dumps[tag].values()) <= 64 << 20
+        assert round(float(dumps[tag]["loss"]), 4) == out["config"]["final_loss"]
+        assert dumps[tag]["logits"].shape == (2 * 256, 20) and dumps[tag]["grad_norm"].shape == (6,)
+    for k in dumps["a"]:
+        assert np.array_equal(dumps["a"][k], dumps["b"][k]), k
+    assert not np.array_equal(dumps["a"]["param_sample"], dumps["c"]["param_sample"])
+
+
+def test_bench_runs_the_prebuilt_library_of_a_read_only_tree(monkeypatch):
+    """bench.py on a built tree this user cannot write (another build compared through --dump-outputs): HIPCC="" sends every
+    build() of the run to the library already built; a writable tree keeps its rebuild-on-demand"""
+    import bench
+    from pointcept_amd import build as B
+
+    monkeypatch.setenv("HIPCC", "unset below; restored after the test")
+    monkeypatch.delenv("HIPCC")
+    monkeypatch.setattr(bench.os, "access", lambda path, mode: True)
+    bench.use_prebuilt_library_if_read_only()
+    assert "HIPCC" not in os.environ
+    monkeypatch.setattr(bench.os, "access", lambda path, mode: False)
+    bench.use_prebuilt_library_if_read_only()
+    assert os.environ["HIPCC"] == ""
+    monkeypatch.setattr(B, "HIPCC", os.environ["HIPCC"])
+    monkeypatch.setattr(B, "_build_locked", None)
+    assert B.build() == B.LIB
+
+
 def test_rank_core_share_is_disjoint_and_numa_local():
     """dp.rank_core_share: even split of the GPU's NUMA-local cores among the ranks on that node, an even slice of the allowed
     cores when the topology is unknown; disjoint across ranks either way"""

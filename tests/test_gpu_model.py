@@ -469,11 +469,12 @@ def test_ptv3_rpe_branch_on_the_kernels_under_autocast(cuda, monkeypatch, amp):
     assert float(res["kernel"][2]["dec.dec0.block0.attn.rpe.rpe_table"].abs().max()) > 0
 
 
-def test_bench_step_under_ddp_over_rccl_single_rank(cuda):
+def test_bench_step_under_ddp_over_rccl_single_rank(cuda, tmp_path):
     """The N > 1 path of bench.py on the one GPU a gpurun box has: PTC_FORCE_DDP=1 initialises the "nccl" (= RCCL) process
     group at world size 1 and wraps the model in DistributedDataParallel (bucket hooks, gradient_as_bucket_view, the
     all-reduce launched on RCCL's stream) around the engine's autograd Functions.  Same seeds with and without the wrapper:
-    the loss after the timed steps must be identical (a one-rank all-reduce averages over one rank)."""
+    the loss after the timed steps must be identical (a one-rank all-reduce averages over one rank).  Both runs also write
+    --dump-outputs: the seg head's logits, gradients and updated parameters of the last step agree as well."""
     import json
     import subprocess
     import sys
@@ -481,16 +482,26 @@ def test_bench_step_under_ddp_over_rccl_single_rank(cuda):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
            "--points", "20000", "--no-secondary", "--no-cpu-baseline"]
-    lines = {}
+    lines, dumps = {}, {}
     for tag, force in (("ddp", "1"), ("plain", "0")):
         env = dict(os.environ, PTC_FORCE_DDP=force, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                    MASTER_PORT="29531")
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / tag)], env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         lines[tag] = json.loads(r.stdout.strip().splitlines()[-1])
+        dumps[tag] = {f.stem: np.load(f) for f in sorted((tmp_path / tag).glob("*.npy"))}
     assert lines["ddp"]["ddp"] is True and lines["plain"]["ddp"] is False
     assert lines["ddp"]["n_gpus"] == 1 and lines["ddp"]["rccl_ranks"] == 1
     assert lines["ddp"]["config"]["final_loss"] == lines["plain"]["config"]["final_loss"], (lines["ddp"]["config"], lines["plain"]["config"])
+    d, p = dumps["ddp"], dumps["plain"]
+    assert set(p) == {"loss", "logits", "grad_norm", "grad_sample", "param_sample"}
+    assert {k: list(a.shape) for k, a in p.items()} == lines["plain"]["dumped_outputs"]["arrays"]
+    assert p["logits"].shape == (min(lines["plain"]["config"]["points_per_gpu"], 1 << 16), 20)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in p.values())
+    assert round(float(p["loss"]), 4) == lines["plain"]["config"]["final_loss"]
+    for k in p:
+        scale = max(float(np.abs(p[k]).max()), 1e-6)
+        assert float(np.abs(d[k] - p[k]).max()) <= 1e-2 * scale, (k, float(np.abs(d[k] - p[k]).max()), scale)
 
 
 def test_ptv3_enable_flash_false_uses_the_shrunk_patch(cuda):

@@ -1073,3 +1073,18 @@ def test_batched_bn_counters_context(monkeypatch):
     monkeypatch.setattr(config, "BATCH_BN_COUNTERS", False)
     with PNN.batched_bn_counters():
         assert PNN._bn_tls.pending is None
+
+
+def test_build_of_an_up_to_date_tree_writes_nothing(monkeypatch):
+    """lib() calls build() on first use: once the library is up to date, build() returns it without creating the build directory
+    or taking its lock, so a built tree that belongs to another user (read-only here) still loads"""
+    from pointcept_amd import build as B
+
+    lib = B.build()
+
+    def refuse(*a, **k):
+        raise AssertionError("build() wrote into an up-to-date tree")
+
+    monkeypatch.setattr(B.os, "makedirs", refuse)
+    monkeypatch.setattr(B, "_build_locked", refuse)
+    assert B.build() == lib
