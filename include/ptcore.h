@@ -473,7 +473,12 @@ int ptc_attn_varlen_hd_rope_bwd(const void* qkv, const void* out, const void* do
  *   rpe_table  : [3 R, H] fp32, R = 2 pos_bnd + 1 (RPE.rpe_table);  d_rpe_table: same shape, overwritten
  * The bias is evaluated per pair in the tile loop; nothing of size L^2 is materialised.  d_rpe_table is accumulated in
  * 2^-24 fixed point with 64-bit integer atomics (order-independent: bit-reproducible, unlike the reference's float
- * atomicAdd) and converted at the end; workspace = ptc_attn_rpe_bwd_workspace_bytes. */
+ * atomicAdd) and converted at the end; workspace = ptc_attn_rpe_bwd_workspace_bytes (enough for every dtype).
+ * dtype: PTC_BF16 or PTC_F16 tensors (qkv, out, dout, dqkv) around bf16 operands with fp32 accumulation, as the flash
+ *   branch; PTC_F32 tensors with fp32 arithmetic throughout (the reference's branch without autocast: exact-f32 MFMA
+ *   16x16x4, fp32 softmax), out / dout / dqkv 16-byte aligned.  The fp32 table gradient uses 2^-44 fixed point (range
+ *   +-2^19 per entry); a head whose sum of |dS| over all pairs reaches 2^18 gets NaN in its column of d_rpe_table
+ *   instead of a wrapped value. */
 int ptc_attn_rpe_fwd(const void* qkv, const int32_t* cu_seqlens, const int32_t* grid_coord,
                      const float* rpe_table, int pos_bnd, int64_t n_seq, int64_t total, int H,
                      int max_seqlen, float softmax_scale, int dtype, void* out, float* lse,

@@ -15,7 +15,8 @@ settings), and so a regression can be bisected without a rebuild.
   PTC_PREFETCH_LEVELS=0  every SerializedPooling fetches its own sizes (two host syncs per stage) instead of the one
                      up-front copy of all level sizes (ptc_pool_level_counts)
   PTC_RPE_KERNEL=0   the RPE attention branch (enable_flash=False, enable_rpe=True) keeps the dense [P,H,K,K] torch
-                     formulation under bf16 autocast instead of the window-attention kernels of csrc/attention_rpe.h
+                     formulation instead of the window-attention kernels of csrc/attention_rpe.h -- under bf16 / fp16 autocast
+                     and in fp32 runs without autocast (csrc/attention_rpe_f32.h) alike
   PTC_EXEC_BLOCK=0   a PT-v3m1 Block is enqueued by ~16 Python autograd Functions (the fused joints below) instead of one C call per
                      direction (csrc/block_exec.hip: same kernels, same operands, bit-identical; ~20 ms less host time per step)
   PTC_WGRAD_BLK=0    the weight gradient of the 32 / 64-channel submanifold convolutions runs on the global-gather kernel (wgrad2) instead

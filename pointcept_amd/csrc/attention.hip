@@ -857,6 +857,7 @@ attn_bwd_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict
 #include "attention_bwd1.h"
 #include "attention_hd.h"
 #include "attention_rpe.h"
+#include "attention_rpe_f32.h"
 #include "attention_drop.h"
 
 // ================================================================================================
@@ -875,12 +876,16 @@ static size_t at_bwd_pad() { const char* e = getenv("PTC_AT_BWD_PAD_LDS"); retur
 static size_t dq_lds_bytes(int lp_max) { return (size_t)lp_max * 64 + at_bwd_pad(); }
 static size_t dkv_lds_bytes(int lp_max) { return (size_t)lp_max * 64 + (size_t)lp_max * 8 + at_bwd_pad(); }
 
+static int check_shapes(const char* name, const void* qkv, const int32_t* cu, int64_t n_seq, int64_t total, int H, int max_seqlen);
 static int check_common(const char* name, const void* qkv, const int32_t* cu, int64_t n_seq, int64_t total, int H,
                         int max_seqlen, int dtype, bool f16_io = false) {
   // f16_io (the head_dim-16 window kernels): PTC_F16 = f16 tensors in and out around the same bf16 arithmetic, i.e. the reference's
   // qkv.to(bfloat16) / feat.to(qkv.dtype) casts folded into the load / store paths (see at_in / at_out)
   PTC_REQUIRE(dtype == PTC_BF16 || (f16_io && dtype == PTC_F16), PTC_EUNSUPPORTED,
               "%s: bf16 arithmetic only (the reference casts qkv to bf16, ptv3m1:209)%s", name, f16_io ? "; tensors bf16 or f16" : "");
+  return check_shapes(name, qkv, cu, n_seq, total, H, max_seqlen);
+}
+static int check_shapes(const char* name, const void* qkv, const int32_t* cu, int64_t n_seq, int64_t total, int H, int max_seqlen) {
   PTC_REQUIRE(n_seq >= 0 && total >= 0 && H >= 1, PTC_EINVAL, "%s: bad sizes", name);
   PTC_REQUIRE(max_seqlen >= 1 && max_seqlen <= AT_MAX_L, PTC_EUNSUPPORTED, "%s: max_seqlen=%d not in [1,%d]", name, max_seqlen, AT_MAX_L);
   PTC_REQUIRE(n_seq * H < (1ll << 29), PTC_EUNSUPPORTED, "%s: grid too large", name);
@@ -1238,7 +1243,9 @@ extern "C" int ptc_attn_varlen_hd_rope_bwd(const void* qkv, const void* out, con
 // ------------------------------------------------------------------------------------------------
 static int rpe_check(const char* name, const void* qkv, const int32_t* cu, const int32_t* gc, const float* table, int pos_bnd,
                      int64_t n_seq, int64_t total, int H, int max_seqlen, int dtype) {
-  int rc = check_common(name, qkv, cu, n_seq, total, H, max_seqlen, dtype, true);
+  // PTC_F32: the reference's branch without autocast, fp32 arithmetic throughout (attention_rpe_f32.h); bf16 / f16 as check_common
+  int rc = dtype == PTC_F32 ? check_shapes(name, qkv, cu, n_seq, total, H, max_seqlen)
+                            : check_common(name, qkv, cu, n_seq, total, H, max_seqlen, dtype, true);
   if (rc != PTC_OK) return rc;
   PTC_REQUIRE(pos_bnd >= 0 && pos_bnd <= 4096, PTC_EINVAL, "%s: pos_bnd=%d out of range", name, pos_bnd);
   PTC_REQUIRE(n_seq == 0 || (gc && table), PTC_EINVAL, "%s: null buffer", name);
@@ -1253,6 +1260,20 @@ extern "C" int ptc_attn_rpe_fwd(const void* qkv, const int32_t* cu_seqlens, cons
   if (n_seq == 0 || total == 0) return PTC_OK;
   PTC_REQUIRE(out && lse, PTC_EINVAL, "ptc_attn_rpe_fwd: null buffer");
   const int lp_max = (max_seqlen + 31) & ~31, R = 2 * pos_bnd + 1;
+  if (dtype == PTC_F32) {
+    PTC_REQUIRE((uintptr_t)out % 16 == 0, PTC_EINVAL, "ptc_attn_rpe_fwd: out must be 16-byte aligned");
+    const size_t lds32 = ar32_fwd_lds(lp_max, R);
+    PTC_REQUIRE(lds32 <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_fwd: max_seqlen=%d with pos_bnd=%d does not fit LDS (fp32)", max_seqlen,
+                pos_bnd);
+    const int n_units = (int)(n_seq * H);
+    rc = allow_big_lds(attn_rpe_fwd_f32_kernel, lds32);
+    if (rc != PTC_OK) return rc;
+    hipLaunchKernelGGL(attn_rpe_fwd_f32_kernel, dim3((unsigned)(8 * ((n_units + 7) / 8))), dim3(AT_THREADS), lds32, (hipStream_t)stream,
+                       (const float*)qkv, cu_seqlens, grid_coord, rpe_table, R, pos_bnd, H, softmax_scale, total, lp_max, n_units,
+                       (float*)out, lse);
+    PTC_CHECK_LAUNCH("attn_rpe_fwd_f32_kernel");
+    return PTC_OK;
+  }
   const size_t lds = (size_t)lp_max * 32 + (size_t)17 * (lp_max + 8) * 2 + 64 + ar_extra_lds(lp_max, R);
   PTC_REQUIRE(lds <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_fwd: max_seqlen=%d with pos_bnd=%d does not fit LDS", max_seqlen, pos_bnd);
   const int n_units = (int)(n_seq * H);
@@ -1272,8 +1293,10 @@ extern "C" int ptc_attn_rpe_fwd(const void* qkv, const int32_t* cu_seqlens, cons
   return PTC_OK;
 }
 
+// delta [H, T] | d table fixed point [3R][H] i64 | (fp32 only) sum of |dS| per head: the larger of the two paths' needs
 extern "C" size_t ptc_attn_rpe_bwd_workspace_bytes(int64_t total, int H, int pos_bnd) {
-  return ptc_attn_varlen_bwd_workspace_bytes(total, H) + ptc_align_up((size_t)3 * (2 * (size_t)(pos_bnd > 0 ? pos_bnd : 0) + 1) * H * 8, 256);
+  return ptc_attn_varlen_bwd_workspace_bytes(total, H) + ptc_align_up((size_t)3 * (2 * (size_t)(pos_bnd > 0 ? pos_bnd : 0) + 1) * H * 8, 256) +
+         ptc_align_up((size_t)(H > 0 ? H : 1) * sizeof(float), 256);
 }
 
 extern "C" int ptc_attn_rpe_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* cu_seqlens,
@@ -1293,6 +1316,34 @@ extern "C" int ptc_attn_rpe_bwd(const void* qkv, const void* out, const void* do
   unsigned long long* dt_fix = (unsigned long long*)((char*)workspace + ptc_attn_varlen_bwd_workspace_bytes(total, H));
   PTC_HIP(hipMemsetAsync(dt_fix, 0, (size_t)3 * R * H * 8, s));
   const int lp_max = (max_seqlen + 31) & ~31;
+  if (dtype == PTC_F32) {
+    PTC_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)dout % 16 == 0 && (uintptr_t)dqkv % 16 == 0, PTC_EINVAL,
+                "ptc_attn_rpe_bwd: out, dout and dqkv must be 16-byte aligned");
+    const size_t lq = ar32_dq_lds(lp_max, R), lkv = ar32_dkv_lds(lp_max, R);
+    PTC_REQUIRE(lkv <= AH_LDS_LIMIT && lq <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_bwd: max_seqlen=%d with pos_bnd=%d does not fit LDS (fp32)",
+                max_seqlen, pos_bnd);
+    float* abs_sum = (float*)((char*)dt_fix + ptc_align_up((size_t)3 * R * H * 8, 256));
+    PTC_HIP(hipMemsetAsync(abs_sum, 0, (size_t)H * sizeof(float), s));
+    const int n_units = (int)(n_seq * H);
+    const unsigned grid = (unsigned)(8 * ((n_units + 7) / 8));
+    float* delta = (float*)workspace;
+    rc = allow_big_lds(attn_rpe_bwd_dq_f32_kernel, lq);
+    if (rc != PTC_OK) return rc;
+    rc = allow_big_lds(attn_rpe_bwd_dkv_f32_kernel, lkv);
+    if (rc != PTC_OK) return rc;
+    hipLaunchKernelGGL(attn_rpe_bwd_dq_f32_kernel, dim3(grid), dim3(AT_THREADS), lq, s, (const float*)qkv, (const float*)out, (const float*)dout,
+                       lse, cu_seqlens, grid_coord, rpe_table, R, pos_bnd, H, softmax_scale, total, lp_max, n_units, (float*)dqkv, delta,
+                       dt_fix, abs_sum);
+    PTC_CHECK_LAUNCH("attn_rpe_bwd_dq_f32_kernel");
+    hipLaunchKernelGGL(attn_rpe_table_finish_f32_kernel, dim3((unsigned)ptc_cdiv((int64_t)3 * R * H, 256)), dim3(256), 0, s,
+                       (const unsigned long long*)dt_fix, (const float*)abs_sum, H, (int64_t)3 * R * H, d_rpe_table);
+    PTC_CHECK_LAUNCH("attn_rpe_table_finish_f32_kernel");
+    hipLaunchKernelGGL(attn_rpe_bwd_dkv_f32_kernel, dim3(grid), dim3(AT_THREADS), lkv, s, (const float*)qkv, (const float*)dout, lse,
+                       (const float*)delta, cu_seqlens, grid_coord, rpe_table, R, pos_bnd, H, softmax_scale, total, lp_max, n_units,
+                       (float*)dqkv);
+    PTC_CHECK_LAUNCH("attn_rpe_bwd_dkv_f32_kernel");
+    return PTC_OK;
+  }
   const size_t lds_q = (size_t)lp_max * 64 + ar_extra_lds(lp_max, R), lds_kv = (size_t)lp_max * 72 + ar_extra_lds(lp_max, R);
   PTC_REQUIRE(lds_kv <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_bwd: max_seqlen=%d with pos_bnd=%d does not fit LDS", max_seqlen, pos_bnd);
   const int n_units = (int)(n_seq * H);

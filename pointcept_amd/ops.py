@@ -978,19 +978,28 @@ def attn_rope_bwd(qkv, out, dout, lse, xyz, inv_freq, cu_seqlens, max_seqlen: in
     return dqkv
 
 
-def attn_rpe_supported(head_dim: int, max_seqlen: int, pos_bnd: int) -> bool:
-    """RPE attention kernels (attention_rpe.h): head_dim 16, windows whose images + coordinates + table fit LDS."""
+def attn_rpe_supported(head_dim: int, max_seqlen: int, pos_bnd: int, dtype: torch.dtype = torch.bfloat16) -> bool:
+    """RPE attention kernels: head_dim 16, windows whose images + coordinates + table fit LDS -- the 16-bit budget of attention_rpe.h for
+    bf16 / f16, the fp32 one of attention_rpe_f32.h (two fp32 window images, lse / delta, coordinates, table) for torch.float32."""
     lp = (int(max_seqlen) + 31) & ~31
     r = 2 * int(pos_bnd) + 1
-    return head_dim == 16 and 1 <= max_seqlen <= 1024 and lp * 72 + lp * 8 + ((3 * r + 3) & ~3) * 8 <= 163840
+    t4 = (3 * r + 3) & ~3
+    if dtype == torch.float32:
+        fits = max(lp * 136 + t4 * 12 + 32, lp * 144 + t4 * 4) <= 163840
+    elif dtype in (torch.bfloat16, torch.float16):
+        fits = lp * 72 + lp * 8 + t4 * 8 <= 163840
+    else:
+        return False
+    return head_dim == 16 and 1 <= max_seqlen <= 1024 and pos_bnd >= 0 and fits
 
 
 def attn_rpe_fwd(qkv, cu_seqlens, max_seqlen: int, softmax_scale: float, grid_coord, rpe_table, pos_bnd: int):
-    """qkv [T,3,H,16] bf16 | f16, grid_coord [T,3] int32 (same row order), rpe_table [3(2B+1),H] fp32 -> (out [T,H,16] like qkv, lse [H,T]).
-    f16 tensors (the reference's fp16 AMP) ride around the same bf16 arithmetic: the casts sit in the kernels' load / store paths."""
+    """qkv [T,3,H,16] bf16 | f16 | fp32, grid_coord [T,3] int32 (same row order), rpe_table [3(2B+1),H] fp32 -> (out [T,H,16] like qkv,
+    lse [H,T] fp32).  f16 tensors (the reference's fp16 AMP) ride around the same bf16 arithmetic: the casts sit in the kernels' load /
+    store paths.  fp32 tensors (no autocast) run the fp32 kernels: fp32 operands, logits, softmax and accumulation."""
     require_cuda(qkv, cu_seqlens, grid_coord, rpe_table)
-    if qkv.dtype not in (torch.bfloat16, torch.float16) or qkv.dim() != 4 or qkv.shape[1] != 3 or qkv.shape[3] != 16:
-        raise PtcoreError(f"qkv must be bf16 / f16 [T,3,H,16], got {qkv.dtype} {tuple(qkv.shape)}")
+    if qkv.dtype not in (torch.bfloat16, torch.float16, torch.float32) or qkv.dim() != 4 or qkv.shape[1] != 3 or qkv.shape[3] != 16:
+        raise PtcoreError(f"qkv must be bf16 / f16 / fp32 [T,3,H,16], got {qkv.dtype} {tuple(qkv.shape)}")
     T, _, H, _ = qkv.shape
     if grid_coord.dtype != torch.int32 or tuple(grid_coord.shape) != (T, 3):
         raise PtcoreError(f"grid_coord must be int32 [{T},3], got {grid_coord.dtype} {tuple(grid_coord.shape)}")
@@ -1006,7 +1015,8 @@ def attn_rpe_fwd(qkv, cu_seqlens, max_seqlen: int, softmax_scale: float, grid_co
 
 
 def attn_rpe_bwd(qkv, out, dout, lse, cu_seqlens, max_seqlen: int, softmax_scale: float, grid_coord, rpe_table, pos_bnd: int):
-    """-> (dqkv like qkv, d_rpe_table fp32 like rpe_table)"""
+    """-> (dqkv like qkv, d_rpe_table fp32 like rpe_table).  qkv / out / dout bf16 | f16 | fp32 (dout is cast to qkv's dtype); the
+    fp32 table gradient is exact to 2^-44 per entry and bit-reproducible, NaN in a head whose sum of |dS| reaches 2^18 (ptcore.h)."""
     require_cuda(qkv, out, dout, lse, cu_seqlens, grid_coord, rpe_table)
     qkv, out = qkv.contiguous(), out.contiguous()
     dout = dout.to(qkv.dtype).contiguous()

@@ -244,13 +244,22 @@ class SerializedAttention(PointModule):
         """RPE branch on the window-attention kernels (attention_rpe.h) instead of the dense [P,H,K,K] formulation: whenever the
         operands are 16-bit anyway -- bf16 or fp16 autocast (the reference's matmuls then run in the autocast dtype whatever the upcast
         flags say; `configs/s3dis/semseg-pt-v3m1-1-rpe.py` runs under the default fp16 AMP): the kernel keeps fp32 logits, softmax and
-        accumulation, fp16 tensors go in and out through its load / store paths around bf16 operands (as in the flash branch) --, no
-        attention dropout is active, head_dim 16.  An fp32 run (no autocast) keeps the torch formulation below BY NAME: `(q * scale) @ k^T`,
-        `torch.softmax`, `attn @ v` on fp32 tensors -- its results must not be rounded to 16 bits (INTEGRATION, stated deviations)."""
+        accumulation, fp16 tensors go in and out through its load / store paths around bf16 operands (as in the flash branch) --, or an
+        fp32 run without autocast (the reference's tester, `enable_amp = False`), which takes the fp32 instances of the same kernels
+        (attention_rpe_f32.h: fp32 operands, logits, softmax and accumulation, nothing rounded to 16 bits); no attention dropout is
+        active, head_dim 16, and the window fits the kernels' LDS budget for that dtype."""
         drop = self.attn_drop.p if isinstance(self.attn_drop, nn.Dropout) else self.attn_drop
-        return (config.RPE_KERNEL and self.rpe is not None and point.feat.is_cuda and torch.is_autocast_enabled("cuda")
-                and torch.get_autocast_dtype("cuda") in (torch.bfloat16, torch.float16) and (drop == 0.0 or not self.training)
-                and ops.attn_rpe_supported(self.channels // self.num_heads, self.patch_size, self.rpe.pos_bnd))
+        if not (config.RPE_KERNEL and self.rpe is not None and point.feat.is_cuda and (drop == 0.0 or not self.training)):
+            return False
+        if torch.is_autocast_enabled("cuda"):
+            dtype = torch.get_autocast_dtype("cuda")
+            if dtype not in (torch.bfloat16, torch.float16):
+                return False
+        elif point.feat.dtype == torch.float32:
+            dtype = torch.float32
+        else:
+            return False
+        return ops.attn_rpe_supported(self.channels // self.num_heads, self.patch_size, self.rpe.pos_bnd, dtype)
 
     def _forward_rpe_kernel(self, point):
         H, K, C = self.num_heads, self.patch_size, self.channels
@@ -261,8 +270,9 @@ class SerializedAttention(PointModule):
         if key not in point.keys():                                   # the role of get_rel_pos' cache (ptv3m1:104-112): O(N), not O(N K)
             point[key] = point.grid_coord[order].to(torch.int32)
         qkv = self.qkv(point.feat)[order]                              # ptv3m1:188
-        q16 = qkv if qkv.dtype in (torch.bfloat16, torch.float16) else qkv.to(torch.bfloat16)
-        out = PF.attn_rpe_qkvpacked(q16.reshape(-1, 3, H, C // H), cu_seqlens, K, self.scale, point[key],
+        # 16-bit under autocast, fp32 without it (the fp32 kernels): never rounded here
+        q_in = qkv if qkv.dtype in (torch.bfloat16, torch.float16, torch.float32) else qkv.to(torch.bfloat16)
+        out = PF.attn_rpe_qkvpacked(q_in.reshape(-1, 3, H, C // H), cu_seqlens, K, self.scale, point[key],
                                     self.rpe.rpe_table, self.rpe.pos_bnd)
         feat = out.reshape(-1, C).to(qkv.dtype)[inverse]               # ptv3m1:206,216
         point.feat = self.proj_drop(self.proj(feat))

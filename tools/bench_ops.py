@@ -377,6 +377,62 @@ def bench_attention_rpe(rows, n_seq, H, L, results):
                 f"dense torch formulation fwd {r['dense_fwd_us']:10.1f} us ([P,H,K,K] fp32 = {n_seq * H * L * L * 4 / 1e9:.2f} GB)")
 
 
+def _peak_mb(fn):
+    """peak allocation of one call above what was allocated before it, MB"""
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+
+def bench_attention_rpe_f32(rows, n_seq, H, L, results):
+    """A13 without autocast: the fp32 RPE kernels (attention_rpe_f32.h) beside the reference's dense formulation in fp32 torch (forward and
+    forward + backward through autograd), time and peak allocated memory of each."""
+    bnd = int((4 * L) ** (1 / 3) * 2)
+    T = n_seq * L
+    qkv = torch.randn(T, 3, H, 16, device=DEV)
+    cu = torch.arange(0, T + 1, L, dtype=torch.int32, device=DEV)
+    gc = torch.randint(0, 2 * bnd, (T, 3), device=DEV, dtype=torch.int32)
+    table = torch.randn(3 * (2 * bnd + 1), H, device=DEV) * 0.02
+    sc = 0.25
+    out, lse = ops.attn_rpe_fwd(qkv, cu, L, sc, gc, table, bnd)
+    do = torch.randn_like(out)
+    r = {"shape": [n_seq, L, H], "pos_bnd": bnd, "dtype": "fp32"}
+    r["fwd_us"] = timeit(lambda: ops.attn_rpe_fwd(qkv, cu, L, sc, gc, table, bnd), iters=5) * 1e6
+    r["bwd_us"] = timeit(lambda: ops.attn_rpe_bwd(qkv, out, do, lse, cu, L, sc, gc, table, bnd), iters=5) * 1e6
+    r["fwd_peak_mb"] = _peak_mb(lambda: ops.attn_rpe_fwd(qkv, cu, L, sc, gc, table, bnd))
+    r["bwd_peak_mb"] = _peak_mb(lambda: ops.attn_rpe_bwd(qkv, out, do, lse, cu, L, sc, gc, table, bnd))
+    del out, lse
+
+    def dense(grad):
+        x = qkv.detach().requires_grad_(grad)
+        t = table.detach().requires_grad_(grad)
+        q, k, v = x.reshape(n_seq, L, 3, H, 16).permute(2, 0, 3, 1, 4).unbind(0)
+        g = gc.reshape(n_seq, L, 3).long()
+        rel = g.unsqueeze(2) - g.unsqueeze(1)
+        idx = rel.clamp(-bnd, bnd) + bnd + torch.arange(3, device=DEV) * (2 * bnd + 1)
+        bias = t.index_select(0, idx.reshape(-1)).view(idx.shape + (-1,)).sum(3).permute(0, 3, 1, 2)
+        attn = torch.softmax((q * sc) @ k.transpose(-2, -1) + bias, dim=-1)
+        o = (attn @ v).transpose(1, 2)
+        if grad:
+            o.backward(do.view(o.shape))
+
+    for tag, grad in (("dense_fwd", False), ("dense_fwd_bwd", True)):
+        try:
+            r[tag + "_us"] = timeit(lambda: dense(grad), iters=3, warm=1) * 1e6
+            r[tag + "_peak_mb"] = _peak_mb(lambda: dense(grad))
+        except RuntimeError as e:   # out of memory at large shapes is the point of the comparison
+            r[tag + "_us"] = r[tag + "_peak_mb"] = float("nan")
+            r[tag + "_error"] = str(e)[:80]
+        torch.cuda.empty_cache()
+    results.append(r)
+    rows.append(f"attention_rpe fp32 n_seq={n_seq:4d} L={L} H={H:2d} bnd={bnd} | kernels: fwd {r['fwd_us']:9.1f} us {r['fwd_peak_mb']:8.1f} MB, "
+                f"bwd {r['bwd_us']:9.1f} us {r['bwd_peak_mb']:8.1f} MB | fp32 torch formulation: fwd {r['dense_fwd_us']:10.1f} us "
+                f"{r['dense_fwd_peak_mb']:9.1f} MB, fwd+bwd {r['dense_fwd_bwd_us']:10.1f} us {r['dense_fwd_bwd_peak_mb']:9.1f} MB")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -441,6 +497,8 @@ def main():
         res["attn_rpe"] = []
         for n_seq, H, L in ((64, 4, 256), (200, 4, 1024), (800, 4, 1024)):
             bench_attention_rpe(rows, n_seq, H, L, res["attn_rpe"])
+        for n_seq, H, L in ((64, 4, 256), (200, 4, 1024), (800, 4, 1024)):
+            bench_attention_rpe_f32(rows, n_seq, H, L, res["attn_rpe"])
     if want("attn_hd"):
         res["attn_hd"] = []
         for n_seq, H, D, L in ((800, 3, 18, 1024), (200, 6, 18, 1024), (48, 12, 18, 1024), (200, 4, 32, 1024), (200, 4, 48, 672), (200, 4, 64, 512)):
