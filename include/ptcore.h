@@ -728,6 +728,38 @@ int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in
 int ptc_ptv3_block_bwd(const int64_t* iv, const float* fv, const void* const* in, const void* const* sv, void* const* g,
                        void* workspace, size_t workspace_bytes, ptc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Q. OA-CNNs adaptive aggregation (pointcept/models/oacnns/oacnns_v1m1_base.py:87-111,160-164), csrc/cluster_agg.hip.
+ * ptc_grid_cluster_count: the grid clusters of every level of a DonwBlock -- torch_geometric's voxel_grid(pos = indices[:, 1:].float(),
+ *   size, batch = indices[:, 0]) followed by torch.unique(return_inverse=True): cells anchored at the GLOBAL per-axis minimum,
+ *   cell = trunc((c - min) / size) in fp32, ids ascending in (batch, z, y, x).  indices [n,4] int32; sizes / spatial_shape HOST
+ *   ([n_levels] cell sizes, [3] exclusive coordinate bounds); outputs order [L,n] (rows in cluster order), cluster [L,n] (ascending
+ *   numbering) and n_cluster [L] int64 on the device.  The CSR of level l: ptc_pool_maps_fill(order[l], cluster[l], n, n_cluster[l]).
+ * ptc_cluster_center: y_l = x_l - mean over the cluster of each row (scatter mean, :92) for all levels in one launch; x_l / y_l [n,c]
+ *   device pointers in HOST arrays [n_levels]; perm = order[l], indptr = CSR of level l; n_cluster HOST.  Its backward is itself.
+ * ptc_cluster_agg_fwd: out[n] = sum_l softmax(a[n])_l S_l[cluster_l[n]], S_l[k] = sum_{m in k} v_l[m] e_l[m] / (sum_{m in k} e_l[m] + 1e-6),
+ *   e_l = exp(u_l - max(u_l)) with one maximum over the whole [n,c] tensor u_l (:93-102).  u_l, v_l [n,c], a [n,L], out [n,c], all of
+ *   `dtype`, fp32 arithmetic.  state (ptc_cluster_agg_state_bytes, fp32) is written here and read by the backward.
+ * ptc_cluster_agg_bwd: du_l, dv_l [n,c], da [n,L] (every element written); the gradient through max(u_l) is spread evenly over the
+ *   elements equal to it.  No float atomics: outputs and gradients are bit-reproducible.
+ * c % 4 == 0, c <= 256, n_levels <= 8.
+ * ------------------------------------------------------------------------------------------ */
+size_t ptc_grid_cluster_workspace_bytes(int64_t n, int n_levels);
+int ptc_grid_cluster_count(const int32_t* indices, int64_t n, const int* sizes, int n_levels, const int* spatial_shape, int batch_size,
+                           int64_t* order, int64_t* cluster, int64_t* n_cluster, void* workspace, size_t workspace_bytes,
+                           ptc_stream_t stream);
+int ptc_cluster_center(const void* const* x, const int64_t* const* perm, const int64_t* const* indptr, const int64_t* n_cluster,
+                       int n_levels, int64_t n, int c, int dtype, void* const* y, ptc_stream_t stream);
+size_t ptc_cluster_agg_state_bytes(int64_t n_cluster_total, int c);
+size_t ptc_cluster_agg_workspace_bytes(int64_t n_cluster_total);
+int ptc_cluster_agg_fwd(const void* const* u, const void* const* v, const void* a, const int64_t* const* perm,
+                        const int64_t* const* indptr, const int64_t* const* cluster, const int64_t* n_cluster, int n_levels, int64_t n,
+                        int c, int dtype, void* out, void* state, size_t state_bytes, ptc_stream_t stream);
+int ptc_cluster_agg_bwd(const void* const* u, const void* const* v, const void* a, const void* dout, const int64_t* const* perm,
+                        const int64_t* const* indptr, const int64_t* const* cluster, const int64_t* n_cluster, int n_levels, int64_t n,
+                        int c, int dtype, const void* state, size_t state_bytes, void* const* du, void* const* dv, void* da,
+                        void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,15 @@ _SIGNATURES = {
     "ptc_aggregation_edge_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
     "ptc_farthest_point_sampling": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
     "ptc_voxel_keys": (c_int, [c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "ptc_grid_cluster_workspace_bytes": (c_size, [c_i64, c_int]),
+    "ptc_grid_cluster_count": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_cluster_center": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_ptr]),
+    "ptc_cluster_agg_state_bytes": (c_size, [c_i64, c_int]),
+    "ptc_cluster_agg_workspace_bytes": (c_size, [c_i64]),
+    "ptc_cluster_agg_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_ptr, c_size,
+                                    c_ptr]),
+    "ptc_cluster_agg_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_size,
+                                    c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "ptc_lovasz_softmax_workspace_bytes": (c_size, [c_i64, c_int]),
     "ptc_lovasz_softmax": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
 }

@@ -50,6 +50,7 @@ HIP_SOURCES = [
     "evalhist.hip",
     "block_exec.hip",
     "mlp.hip",
+    "cluster_agg.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

@@ -14,7 +14,9 @@ import sys
 import types
 
 
-def install(force: bool = False) -> None:
+def install(force: bool = False, geometric: bool = False) -> None:
+    """geometric=True also provides torch_geometric.{nn.pool.voxel_grid, utils.scatter} (torch_geometric_api), which OA-CNNs' and
+    PTv2's files import; opt-in, so that the default install leaves a caller's own torch_geometric (or stand-in) untouched."""
     from . import flash_attn_api, pointops2_api, pointops_api, pointrope_api, spconv_api, torch_scatter_api
 
     def put(name, module):
@@ -44,6 +46,15 @@ def install(force: bool = False) -> None:
     put("pointops2.functions", p2f)
     put("pointops2.functions.pointops", pointops2_api)
     put("pointrope", pointrope_api)      # libs/pointrope: `import pointrope as _kernels` (litept_v1.py:26)
+    if geometric:
+        from . import torch_geometric_api as tg
+
+        top = types.ModuleType("torch_geometric")
+        top.nn, top.utils = tg.nn, tg.utils
+        put("torch_geometric", top)
+        put("torch_geometric.nn", tg.nn)
+        put("torch_geometric.nn.pool", tg.nn.pool)
+        put("torch_geometric.utils", tg.utils)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -57,12 +68,17 @@ MODEL_CLASSES = {                                   # registry name (reference f
     "SpUNet-v1m1": ("sparse_unet", "SpUNetBase"),                     # spconv_unet_v1m1_base.py:88
     "SpUNetNoSkipBase": ("sparse_unet", "SpUNetNoSkipBase"),          # spconv_unet_v1m1_base.py:283 (registered under its class name)
 }
+# ports registered only when named: register_models(MODELS, names=["OACNNs"])
+OPT_IN_MODEL_CLASSES = {
+    "OACNNs": ("oacnns", "OACNNs"),                                   # oacnns_v1m1_base.py:212
+}
 
 
 def register_models(registry, names=None, force: bool = True) -> list:
     """Registers the engine's module-level ports in the reference's `MODELS` registry (pointcept/models/builder.py) under the
     names the reference's configs use, replacing the CUDA-library implementations (`force=True`), so that
-    `MODELS.build(cfg.model.backbone)` constructs them.  Returns the names registered.
+    `MODELS.build(cfg.model.backbone)` constructs them.  Returns the names registered.  Without `names`: every name of
+    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs) only when named.
 
         from pointcept.models.builder import MODELS
         import pointcept_amd.compat; pointcept_amd.compat.register_models(MODELS)
@@ -71,7 +87,7 @@ def register_models(registry, names=None, force: bool = True) -> list:
 
     done = []
     for name in (names or MODEL_CLASSES):
-        mod, cls = MODEL_CLASSES[name]
+        mod, cls = MODEL_CLASSES[name] if name in MODEL_CLASSES else OPT_IN_MODEL_CLASSES[name]
         registry.register_module(name, force=force, module=getattr(importlib.import_module(f"{__package__}.{mod}"), cls))
         done.append(name)
     return done

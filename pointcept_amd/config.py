@@ -28,6 +28,9 @@ settings), and so a regression can be bisected without a rebuild.
                      (round 6; forward and input gradient; profiles/r06_t_conv8_himg.txt)
   PTC_BLK_MLP_FUSED=0  the MLP of a 32- / 64-channel Block runs on the split kernels (fc1 + GELU, fc2 + joint; GELU' input gradient,
                      fc1 input gradient, two weight gradients) instead of csrc/mlp.hip's one kernel per direction (round 6)
+  PTC_OACNN_AGG=0    OA-CNNs' segmented centering and adaptive aggregation (oacnns.py) run as the reference's ATen expression
+                     (exp / index_add scatters / softmax / einsum) instead of csrc/cluster_agg.hip (A/B baseline; the grid clusters
+                     stay on the kernels either way)
   PTC_FUSE_BLOCK=0   the three residual joints of a PTv3 Block run as separate LayerNorm / add / cast
                      kernels instead of the fused add_norm passes
 """
@@ -52,6 +55,7 @@ CONV8 = _flag("PTC_CONV8", True)                      # also read by the C side 
 MLP_ONE_KERNEL = _flag("PTC_BLK_MLP_FUSED", True)     # the same variable switches the block executor's C side (block_exec.hip)
 PREFETCH_LEVELS = _flag("PTC_PREFETCH_LEVELS", True)
 RPE_KERNEL = _flag("PTC_RPE_KERNEL", True)
+OACNN_AGG = _flag("PTC_OACNN_AGG", True)
 WGRAD_BLK = _flag("PTC_WGRAD_BLK", True)
 FUSE_BN_TAIL = _flag("PTC_FUSE_BN_TAIL", True)
 BATCH_BN_COUNTERS = _flag("PTC_BATCH_BN_COUNTERS", True)

@@ -1154,3 +1154,79 @@ def mlp_gelu_supported(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor) -> b
 
 def mlp_gelu(x, w1, b1, w2, b2):
     return _MLP.apply(x, w1, b1, w2, b2)
+
+
+# ------------------------------------------------------------------------------------------------
+# OA-CNNs adaptive aggregation (csrc/cluster_agg.hip)
+# ------------------------------------------------------------------------------------------------
+class _ClusterCenter(Function):
+    @staticmethod
+    def forward(ctx, gc, *xs):
+        ctx.gc = gc
+        return tuple(ops.cluster_center(list(xs), gc))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gys):
+        # y = x - mean_c(x)[c] is a symmetric projection: its backward is the same operator on dy
+        gys = [g.contiguous() if g is not None else None for g in gys]
+        if any(g is None for g in gys):
+            ref = next(g for g in gys if g is not None)
+            gys = [torch.zeros_like(ref) if g is None else g for g in gys]
+        return (None, *ops.cluster_center(gys, ctx.gc))
+
+
+def cluster_center(xs, gc: "ops.GridClusters") -> list:
+    """[x_l - scatter(x_l, cluster_l, reduce="mean")[cluster_l] for every level] (oacnns_v1m1_base.py:92) in one launch per pass."""
+    dt = xs[0].dtype
+    return list(_ClusterCenter.apply(gc, *[x.to(dt).contiguous() for x in xs]))
+
+
+class _ClusterAgg(Function):
+    @staticmethod
+    def forward(ctx, gc, a, *uv):
+        L = gc.levels
+        us, vs = list(uv[:L]), list(uv[L:])
+        out, state = ops.cluster_agg_fwd(us, vs, a, gc)
+        ctx.gc = gc
+        ctx.save_for_backward(a, state, *us, *vs)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        a, state, *uv = ctx.saved_tensors
+        L = ctx.gc.levels
+        du, dv, da = ops.cluster_agg_bwd(uv[:L], uv[L:], a, dout, state, ctx.gc)
+        return (None, da, *du, *dv)
+
+
+def cluster_agg(us, vs, a: torch.Tensor, gc: "ops.GridClusters") -> torch.Tensor:
+    """sum_l softmax(a)_l * scatter(v_l * pw_l, cluster_l)[cluster_l],  pw_l = e_l / (scatter(e_l, cluster_l)[cluster_l] + 1e-6),
+    e_l = exp(u_l - u_l.max())  (oacnns_v1m1_base.py:93-102) on csrc/cluster_agg.hip.  Operands are taken in the dtype of u_0 (the
+    16-bit type under autocast); arithmetic is fp32."""
+    dt = us[0].dtype
+    c = lambda t: t.to(dt).contiguous()   # noqa: E731
+    return _ClusterAgg.apply(gc, c(a), *[c(u) for u in us], *[c(v) for v in vs])
+
+
+def cluster_center_torch(xs, gc: "ops.GridClusters") -> list:
+    """PTC_OACNN_AGG=0: the reference's expression of :92 (ATen index_add scatter)."""
+    out = []
+    for x, cl, n_c in zip(xs, gc.cluster, gc.n_cluster):
+        s = x.new_zeros((n_c, x.shape[1])).index_add(0, cl, x)
+        cnt = torch.bincount(cl, minlength=n_c).clamp(min=1).to(x.dtype)
+        out.append(x - (s / cnt[:, None])[cl])
+    return out
+
+
+def cluster_agg_torch(us, vs, a: torch.Tensor, gc: "ops.GridClusters") -> torch.Tensor:
+    """PTC_OACNN_AGG=0: the reference's expression of :93-102 (ATen exp / index_add / softmax / einsum)."""
+    feats = []
+    for u, v, cl, n_c in zip(us, vs, gc.cluster, gc.n_cluster):
+        pw = torch.exp(u - u.max())
+        pw = pw / (pw.new_zeros((n_c, pw.shape[1])).index_add(0, cl, pw)[cl] + 1e-6)
+        pf = v * pw
+        feats.append(pf.new_zeros((n_c, pf.shape[1])).index_add(0, cl, pf)[cl])
+    adp = torch.softmax(a, dim=1)
+    return torch.einsum("l n, l n c -> l c", adp, torch.stack(feats, dim=1))

@@ -1372,3 +1372,127 @@ def pair_aggregate_bwd(g, attn, v, i0, i1, table_v, rel_idx, want_attn=True, wan
                                        ptr(dv), ptr(dtv), stream_ptr()), "ptc_pair_aggregate_bwd")
     return da, dv, dtv
 
+
+
+# ------------------------------------------------------------------------------------------------
+# OA-CNNs adaptive aggregation (csrc/cluster_agg.hip)
+# ------------------------------------------------------------------------------------------------
+class GridClusters:
+    """The grid clusters of every level of one DonwBlock (oacnns_v1m1_base.py:160-164): per level the inverse `cluster` [N] int64
+    (torch.unique's numbering), `order` [N] int64 (rows in cluster order), the CSR `indptr` [n_cluster + 1] and `n_cluster` (host)."""
+
+    def __init__(self, order, cluster, indptr, n_cluster):
+        self.order, self.cluster, self.indptr, self.n_cluster = order, cluster, indptr, n_cluster
+
+    @property
+    def levels(self) -> int:
+        return len(self.n_cluster)
+
+    def _arrays(self):
+        L = self.levels
+        return ((ctypes.c_void_p * L)(*[ptr(t) for t in self.order]), (ctypes.c_void_p * L)(*[ptr(t) for t in self.indptr]),
+                (ctypes.c_void_p * L)(*[ptr(t) for t in self.cluster]), (ctypes.c_int64 * L)(*self.n_cluster))
+
+
+def grid_clusters(indices: torch.Tensor, sizes: Sequence[int], spatial_shape: Sequence[int], batch_size: int) -> GridClusters:
+    """voxel_grid(indices[:, 1:].float(), size, indices[:, 0]) + torch.unique(return_inverse=True) for every size at once: one key
+    pass, one sort of L rows, one count per level and ONE host read (the L cluster counts) for the whole block."""
+    require_cuda(indices)
+    if indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[1] != 4:
+        raise PtcoreError("grid_clusters: indices must be int32 [N, 4] (batch, x, y, z)")
+    if any(int(s) != s or int(s) < 1 for s in sizes):
+        raise PtcoreError(f"grid_clusters: cell sizes must be positive integers, got {list(sizes)}")
+    ind = indices.contiguous()
+    n, L = ind.shape[0], len(sizes)
+    dev = ind.device
+    order = torch.empty((L, n), dtype=torch.int64, device=dev)
+    cluster = torch.empty((L, n), dtype=torch.int64, device=dev)
+    ncl = torch.empty(L, dtype=torch.int64, device=dev)
+    nbytes = lib().ptc_grid_cluster_workspace_bytes(n, L)
+    ws = _ws(nbytes, dev)
+    sz = (ctypes.c_int * L)(*[int(s) for s in sizes])
+    shp = (ctypes.c_int * 3)(*[int(s) for s in spatial_shape])
+    check(lib().ptc_grid_cluster_count(ptr(ind), n, ctypes.cast(sz, ctypes.c_void_p), L, ctypes.cast(shp, ctypes.c_void_p), int(batch_size),
+                                       ptr(order), ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr()), "ptc_grid_cluster_count")
+    n_cluster = [int(v) for v in ncl.tolist()]
+    indptr = []
+    for l in range(L):
+        ip = torch.empty(n_cluster[l] + 1, dtype=torch.int64, device=dev)
+        head = torch.empty(n_cluster[l], dtype=torch.int64, device=dev)
+        check(lib().ptc_pool_maps_fill(ptr(order[l]), ptr(cluster[l]), n, n_cluster[l], ptr(ip), ptr(head), stream_ptr()), "ptc_pool_maps_fill")
+        indptr.append(ip)
+    return GridClusters(list(order.unbind(0)), list(cluster.unbind(0)), indptr, n_cluster)
+
+
+def _agg_rows(ts, n: int, c: int, dtype, what: str):
+    for t in ts:
+        if t.dtype != dtype or t.shape != (n, c) or not t.is_contiguous():
+            raise PtcoreError(f"{what}: every level tensor must be contiguous [{n}, {c}] {dtype}, got {tuple(t.shape)} {t.dtype}")
+
+
+def cluster_center(xs: Sequence[torch.Tensor], gc: GridClusters) -> list:
+    """y_l = x_l - scatter_mean(x_l, cluster_l)[cluster_l] for every level in one launch (oacnns_v1m1_base.py:92)."""
+    require_cuda(*xs)
+    L = gc.levels
+    if len(xs) != L:
+        raise PtcoreError(f"cluster_center: {len(xs)} tensors for {L} levels")
+    xs = [x.contiguous() for x in xs]
+    n, c = xs[0].shape
+    _agg_rows(xs, n, c, xs[0].dtype, "cluster_center")
+    ys = [torch.empty_like(x) for x in xs]
+    perm, ip, _, ncl = gc._arrays()
+    xa = (ctypes.c_void_p * L)(*[ptr(x) for x in xs])
+    ya = (ctypes.c_void_p * L)(*[ptr(y) for y in ys])
+    check(lib().ptc_cluster_center(ctypes.cast(xa, ctypes.c_void_p), ctypes.cast(perm, ctypes.c_void_p), ctypes.cast(ip, ctypes.c_void_p),
+                                   ctypes.cast(ncl, ctypes.c_void_p), L, n, c, dtype_code(xs[0]), ctypes.cast(ya, ctypes.c_void_p), stream_ptr()),
+          "ptc_cluster_center")
+    return ys
+
+
+def cluster_agg_fwd(us: Sequence[torch.Tensor], vs: Sequence[torch.Tensor], a: torch.Tensor, gc: GridClusters):
+    """out[n] = sum_l softmax(a[n])_l S_l[cluster_l[n]] (oacnns_v1m1_base.py:93-102) -> (out [N, C], state for the backward)."""
+    require_cuda(*us, *vs, a)
+    L = gc.levels
+    if len(us) != L or len(vs) != L:
+        raise PtcoreError(f"cluster_agg_fwd: {len(us)} / {len(vs)} tensors for {L} levels")
+    n, c = us[0].shape
+    dt = us[0].dtype
+    _agg_rows(us, n, c, dt, "cluster_agg_fwd")
+    _agg_rows(vs, n, c, dt, "cluster_agg_fwd")
+    if a.dtype != dt or a.shape != (n, L) or not a.is_contiguous():
+        raise PtcoreError(f"cluster_agg_fwd: a must be contiguous [{n}, {L}] {dt}, got {tuple(a.shape)} {a.dtype}")
+    tot = sum(gc.n_cluster)
+    sbytes = lib().ptc_cluster_agg_state_bytes(tot, c)
+    state = torch.empty(sbytes, dtype=torch.uint8, device=a.device)
+    out = torch.empty((n, c), dtype=dt, device=a.device)
+    perm, ip, cl, ncl = gc._arrays()
+    ua = (ctypes.c_void_p * L)(*[ptr(t) for t in us])
+    va = (ctypes.c_void_p * L)(*[ptr(t) for t in vs])
+    V = ctypes.c_void_p
+    check(lib().ptc_cluster_agg_fwd(ctypes.cast(ua, V), ctypes.cast(va, V), ptr(a), ctypes.cast(perm, V), ctypes.cast(ip, V), ctypes.cast(cl, V),
+                                    ctypes.cast(ncl, V), L, n, c, dtype_code(a), ptr(out), ptr(state), sbytes, stream_ptr()), "ptc_cluster_agg_fwd")
+    return out, state
+
+
+def cluster_agg_bwd(us, vs, a, dout: torch.Tensor, state: torch.Tensor, gc: GridClusters):
+    """-> (du list, dv list, da): the gradients of cluster_agg_fwd, bit-reproducible (no float atomics)."""
+    require_cuda(*us, *vs, a, dout, state)
+    L = gc.levels
+    n, c = us[0].shape
+    dt = us[0].dtype
+    dout = dout.to(dt).contiguous()
+    _agg_rows([dout], n, c, dt, "cluster_agg_bwd")
+    tot = sum(gc.n_cluster)
+    du = [torch.empty_like(t) for t in us]
+    dv = [torch.empty_like(t) for t in vs]
+    da = torch.empty_like(a)
+    wbytes = lib().ptc_cluster_agg_workspace_bytes(tot)
+    ws = _ws(wbytes, a.device)
+    perm, ip, cl, ncl = gc._arrays()
+    V = ctypes.c_void_p
+    keep = [(V * L)(*[ptr(t) for t in ts]) for ts in (us, vs, du, dv)]
+    check(lib().ptc_cluster_agg_bwd(ctypes.cast(keep[0], V), ctypes.cast(keep[1], V), ptr(a), ptr(dout), ctypes.cast(perm, V), ctypes.cast(ip, V),
+                                    ctypes.cast(cl, V), ctypes.cast(ncl, V), L, n, c, dtype_code(a), ptr(state), state.numel(),
+                                    ctypes.cast(keep[2], V), ctypes.cast(keep[3], V), ptr(da), ptr(ws), wbytes, stream_ptr()),
+          "ptc_cluster_agg_bwd")
+    return du, dv, da

@@ -433,10 +433,65 @@ def bench_attention_rpe_f32(rows, n_seq, H, L, results):
                 f"{r['dense_fwd_peak_mb']:9.1f} MB, fwd+bwd {r['dense_fwd_bwd_us']:10.1f} us {r['dense_fwd_bwd_peak_mb']:9.1f} MB")
 
 
+def oacnns_stage_indices(scenes=4, points=100000, stages=4):
+    """int32 [N, 4] indices of every encoder stage of OA-CNNs on a synthetic ScanNet batch (k2 s2 down convs: coordinates halved,
+    one row per coarse site), with the spatial shapes the engine declares"""
+    from pointcept_amd import synthetic
+
+    b = synthetic.collate([synthetic.indoor_scene(31 + i, points) for i in range(scenes)])
+    gc = torch.from_numpy(b["grid_coord"]).to(DEV).long()
+    bt = torch.repeat_interleave(torch.arange(scenes, device=DEV), torch.diff(torch.from_numpy(b["offset"]).to(DEV), prepend=torch.zeros(1, device=DEV, dtype=torch.int64)))
+    shape = [int(m) + 96 for m in gc.max(0).values]
+    out = []
+    for _ in range(stages):
+        gc = gc // 2
+        shape = [(s - 2) // 2 + 1 for s in shape]
+        key = torch.unique(torch.cat([bt[:, None], gc], 1), dim=0)
+        bt, gc = key[:, 0], key[:, 1:]
+        out.append((key.int().contiguous(), list(shape)))
+    return out
+
+
+def bench_oacnns(rows, results, dt=torch.bfloat16):
+    """OA-CNNs' adaptive aggregation (csrc/cluster_agg.hip) at the row counts of each encoder stage of a 4 x 100 000-voxel ScanNet batch
+    (configs/scannet/semseg-oacnns-v1m1-0-base.py: L = 4 levels, 64 / 64 / 128 / 256 channels): the grid-cluster maps of one DonwBlock,
+    centering forward + backward and aggregation forward + backward against the reference's ATen expression (PTC_OACNN_AGG=0)"""
+    from pointcept_amd import functional as PF
+
+    sizes = [[8, 12, 16, 16], [6, 9, 12, 12], [4, 6, 8, 8], [3, 4, 6, 6]]
+    chans = [64, 64, 128, 256]
+    e = torch.tensor([], dtype=dt).element_size()
+    for s, (ind, shape) in enumerate(oacnns_stage_indices()):
+        n, c, L = ind.shape[0], chans[s], len(sizes[s])
+        t_map = timeit(lambda: ops.grid_clusters(ind, sizes[s], shape, 4), iters=10)
+        gc = ops.grid_clusters(ind, sizes[s], shape, 4)
+        us = [torch.randn(n, c, device=DEV).to(dt).requires_grad_() for _ in range(L)]
+        vs = [torch.randn(n, c, device=DEV).to(dt).requires_grad_() for _ in range(L)]
+        a = torch.randn(n, L, device=DEV).to(dt).requires_grad_()
+        g = torch.randn(n, c, device=DEV).to(dt)
+
+        def agg(f):
+            return lambda: torch.autograd.backward(f(us, vs, a, gc), g)
+
+        def center(f):
+            return lambda: torch.autograd.backward(f(us, gc), [g] * L)
+
+        t_k, t_t = timeit(agg(PF.cluster_agg)), timeit(agg(PF.cluster_agg_torch))
+        t_ck, t_ct = timeit(center(PF.cluster_center)), timeit(center(PF.cluster_center_torch))
+        by = (6 * L + 2) * n * c * e            # compulsory: fwd reads u, v, a / writes out; bwd reads u, v, a, dout / writes du, dv, da
+        by_c = 4 * L * n * c * e
+        results.append({"stage": s, "n": n, "c": c, "L": L, "clusters": list(gc.n_cluster), "maps_us": round(t_map * 1e6, 1),
+                        "agg_kernel": roof(by, 0.0, t_k), "agg_torch": roof(by, 0.0, t_t),
+                        "center_kernel": roof(by_c, 0.0, t_ck), "center_torch": roof(by_c, 0.0, t_ct)})
+        rows.append(f"oacnns stage {s} n={n:6d} c={c:3d} L={L} | maps {t_map * 1e6:7.1f} us | agg f+b kernel {t_k * 1e6:8.1f} us "
+                    f"({by / t_k / 1e9:5.0f} GB/s, roof {results[-1]['agg_kernel']['roof_frac']}) torch {t_t * 1e6:8.1f} us | center f+b "
+                    f"kernel {t_ck * 1e6:7.1f} us torch {t_ct * 1e6:7.1f} us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default="", help="comma list of sections: linear,ln,attn,attn_hd,spconv,stages,losses,front")
+    ap.add_argument("--only", default="", help="comma list of sections: linear,ln,attn,attn_hd,spconv,stages,losses,front (opt-in: oacnns, ...)")
     args = ap.parse_args()
     only = set(x for x in args.only.split(",") if x)
     want = lambda name: not only or name in only  # noqa: E731
@@ -486,6 +541,9 @@ def main():
             res["wgrad_small"].append({"shape": [n, cin, cout], "own": roof(by, fl, t_own), "lib": roof(by, fl, t_lib)})
             rows.append(f"wgrad n={n:6d} {cin:4d}->{cout:4d} | own {t_own * 1e6:7.1f} us  lib {t_lib * 1e6:7.1f} us | roof frac own "
                         f"{res['wgrad_small'][-1]['own']['roof_frac']}")
+    if "oacnns" in only:
+        res["oacnns"] = []
+        bench_oacnns(rows, res["oacnns"])
     if want("ln"):
         for n, c in stages:
             bench_ln(rows, n, c, res["ln"])
