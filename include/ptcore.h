@@ -760,6 +760,49 @@ int ptc_cluster_agg_bwd(const void* const* u, const void* const* v, const void* 
                         int c, int dtype, const void* state, size_t state_bytes, void* const* du, void* const* dv, void* da,
                         void* workspace, size_t workspace_bytes, ptc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * R. PointGroup clustering and heads (libs/pointgroup_ops: bfs_cluster_kernel.cu:16-61, bfs_cluster.cpp:53-145;
+ *    pointcept/models/point_group/point_group_v1m1_base.py:72-91,101-179), csrc/pg_cluster.hip.
+ * ptc_pg_ball_query_count / _fill: neighbours of each point i -- same batch index, fp32 d2 (unfused, the reference's order) <
+ *   radius*radius, itself included, none for a non-finite coordinate -- in ascending index order, truncated to the first 1000.
+ *   xyz [n,3] fp32, batch_idxs [n] int32 in [0, n_batch).  count writes start_len [n,2] int32 (exclusive-scan starts, exact lengths)
+ *   and total [2] int64 on the device: (nActive, number of truncated lists, i.e. more than 1000 neighbours).  fill writes idx
+ *   [nActive] int32 and needs the SAME workspace, untouched, after the count.
+ * ptc_pg_cluster_count / _fill: bfs_cluster of (label [n] int32, idx, start_len [n,2]) with `threshold`: the reference's clusters,
+ *   numbered by seed (their smallest index), members in ascending point order.  count writes counts [2] int32 on the device
+ *   (nCluster, sumNPoint); fill writes cluster_idxs [sumNPoint,2] (cluster, point) and cluster_offsets [nCluster+1] int32 from the
+ *   same workspace.  A list of >= 1000 entries is taken as possibly truncated (its component follows the sequential rule exactly).
+ *   skip_negative != 0: clusters whose seed has a negative label are dropped (the model marks its ignored points so, with no
+ *   neighbours, instead of compacting them).
+ * ptc_pg_proposal_scores: per cluster k: count[k], cls[k] = label[seed], score[k] = mean over members m of
+ *   softmax(logits[row(m)])[cls[k]] in fp32 (row(m) = point_map[m] or m); logits [n_rows, c] of `dtype`.
+ * ptc_pg_proposal_masks: out [n_rows_out, n_points] int32 = 1 at (row[cluster], point_map[point]) for clusters with row >= 0.
+ * ptc_pg_bias_loss_fwd: out [3] fp32 = (masked L1, masked negative cosine, sum(mask)) of bias_pred [n,3] (`dtype`) against
+ *   bias_gt = centroid - coord (fp32), mask = instance != ignore_index (int64); fixed-order two-level reductions.
+ * ptc_pg_bias_loss_bwd: dbias_pred [n,3] (`dtype`) from dout [2] = (d l1, d cos) and the forward's out.  No float atomics anywhere.
+ * ------------------------------------------------------------------------------------------ */
+size_t ptc_pg_ball_query_workspace_bytes(int64_t n);
+int ptc_pg_ball_query_count(const float* xyz, const int32_t* batch_idxs, int64_t n, int n_batch, float radius, int32_t* start_len,
+                            int64_t* total, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+int ptc_pg_ball_query_fill(const float* xyz, int64_t n, float radius, const int32_t* start_len, int32_t* idx, void* workspace,
+                           size_t workspace_bytes, ptc_stream_t stream);
+size_t ptc_pg_cluster_workspace_bytes(int64_t n);
+int ptc_pg_cluster_count(const int32_t* label, const int32_t* idx, const int32_t* start_len, int64_t n, int threshold, int skip_negative,
+                         int32_t* counts,
+                         void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+int ptc_pg_cluster_fill(int64_t n, int64_t n_cluster, int64_t n_sum, int32_t* cluster_idxs, int32_t* cluster_offsets, void* workspace,
+                        size_t workspace_bytes, ptc_stream_t stream);
+int ptc_pg_proposal_scores(const void* logits, int dtype, int64_t n_rows, int c, const int32_t* label, const int32_t* cluster_idxs,
+                           const int32_t* cluster_offsets, int64_t n_cluster, const int64_t* point_map, int32_t* count, int32_t* cls,
+                           float* score, ptc_stream_t stream);
+int ptc_pg_proposal_masks(const int32_t* cluster_idxs, int64_t n_sum, const int64_t* row, const int64_t* point_map, int64_t n_points,
+                          int64_t n_rows_out, int32_t* out, ptc_stream_t stream);
+size_t ptc_pg_bias_loss_workspace_bytes(int64_t n);
+int ptc_pg_bias_loss_fwd(const void* bias_pred, int dtype, const float* coord, const float* centroid, const int64_t* instance, int64_t n,
+                         int64_t ignore_index, float* out, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+int ptc_pg_bias_loss_bwd(const void* bias_pred, int dtype, const float* coord, const float* centroid, const int64_t* instance, int64_t n,
+                         int64_t ignore_index, const float* dout, const float* fwd_out, void* dbias_pred, ptc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

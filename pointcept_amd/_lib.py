@@ -148,6 +148,17 @@ _SIGNATURES = {
                                     c_ptr]),
     "ptc_cluster_agg_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_size,
                                     c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_pg_ball_query_workspace_bytes": (c_size, [c_i64]),
+    "ptc_pg_ball_query_count": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_pg_ball_query_fill": (c_int, [c_ptr, c_i64, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_pg_cluster_workspace_bytes": (c_size, [c_i64]),
+    "ptc_pg_cluster_count": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_pg_cluster_fill": (c_int, [c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_pg_proposal_scores": (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "ptc_pg_proposal_masks": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    "ptc_pg_bias_loss_workspace_bytes": (c_size, [c_i64]),
+    "ptc_pg_bias_loss_fwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_pg_bias_loss_bwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     "ptc_lovasz_softmax_workspace_bytes": (c_size, [c_i64, c_int]),
     "ptc_lovasz_softmax": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
 }

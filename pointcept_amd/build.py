@@ -51,6 +51,7 @@ HIP_SOURCES = [
     "block_exec.hip",
     "mlp.hip",
     "cluster_agg.hip",
+    "pg_cluster.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

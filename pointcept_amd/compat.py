@@ -14,9 +14,10 @@ import sys
 import types
 
 
-def install(force: bool = False, geometric: bool = False) -> None:
+def install(force: bool = False, geometric: bool = False, pointgroup: bool = False) -> None:
     """geometric=True also provides torch_geometric.{nn.pool.voxel_grid, utils.scatter} (torch_geometric_api), which OA-CNNs' and
-    PTv2's files import; opt-in, so that the default install leaves a caller's own torch_geometric (or stand-in) untouched."""
+    PTv2's files import; opt-in, so that the default install leaves a caller's own torch_geometric (or stand-in) untouched.
+    pointgroup=True also provides `pointgroup_ops` (pointgroup_ops_api), which PointGroup's files import; opt-in likewise."""
     from . import flash_attn_api, pointops2_api, pointops_api, pointrope_api, spconv_api, torch_scatter_api
 
     def put(name, module):
@@ -55,6 +56,10 @@ def install(force: bool = False, geometric: bool = False) -> None:
         put("torch_geometric.nn", tg.nn)
         put("torch_geometric.nn.pool", tg.nn.pool)
         put("torch_geometric.utils", tg.utils)
+    if pointgroup:
+        from . import pointgroup_ops_api
+
+        put("pointgroup_ops", pointgroup_ops_api)     # libs/pointgroup_ops: `from pointgroup_ops import ballquery_batch_p, bfs_cluster`
 
 
 # ------------------------------------------------------------------------------------------------
@@ -71,6 +76,8 @@ MODEL_CLASSES = {                                   # registry name (reference f
 # ports registered only when named: register_models(MODELS, names=["OACNNs"])
 OPT_IN_MODEL_CLASSES = {
     "OACNNs": ("oacnns", "OACNNs"),                                   # oacnns_v1m1_base.py:212
+    "PG-v1m1": ("point_group", "PointGroup"),                         # point_group_v1m1_base.py:22
+    "PG-v1m2": ("point_group", "PointGroupV1m2"),                     # point_group_v1m2_custom_criteria.py:25
 }
 
 
@@ -78,7 +85,7 @@ def register_models(registry, names=None, force: bool = True) -> list:
     """Registers the engine's module-level ports in the reference's `MODELS` registry (pointcept/models/builder.py) under the
     names the reference's configs use, replacing the CUDA-library implementations (`force=True`), so that
     `MODELS.build(cfg.model.backbone)` constructs them.  Returns the names registered.  Without `names`: every name of
-    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs) only when named.
+    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs, PointGroup) only when named.
 
         from pointcept.models.builder import MODELS
         import pointcept_amd.compat; pointcept_amd.compat.register_models(MODELS)

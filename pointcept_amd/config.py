@@ -31,6 +31,9 @@ settings), and so a regression can be bisected without a rebuild.
   PTC_OACNN_AGG=0    OA-CNNs' segmented centering and adaptive aggregation (oacnns.py) run as the reference's ATen expression
                      (exp / index_add scatters / softmax / einsum) instead of csrc/cluster_agg.hip (A/B baseline; the grid clusters
                      stay on the kernels either way)
+  PTC_PG_CLUSTER=0   PointGroup's clustering, proposal scores and offset losses (point_group.py, pointgroup_ops_api) run as the
+                     torch formulation: chunked brute-force ball query, host BFS, the reference's loss expression (A/B baseline and
+                     cross-check of csrc/pg_cluster.hip)
   PTC_FUSE_BLOCK=0   the three residual joints of a PTv3 Block run as separate LayerNorm / add / cast
                      kernels instead of the fused add_norm passes
 """
@@ -56,6 +59,7 @@ MLP_ONE_KERNEL = _flag("PTC_BLK_MLP_FUSED", True)     # the same variable switch
 PREFETCH_LEVELS = _flag("PTC_PREFETCH_LEVELS", True)
 RPE_KERNEL = _flag("PTC_RPE_KERNEL", True)
 OACNN_AGG = _flag("PTC_OACNN_AGG", True)
+PG_CLUSTER = _flag("PTC_PG_CLUSTER", True)
 WGRAD_BLK = _flag("PTC_WGRAD_BLK", True)
 FUSE_BN_TAIL = _flag("PTC_FUSE_BN_TAIL", True)
 BATCH_BN_COUNTERS = _flag("PTC_BATCH_BN_COUNTERS", True)

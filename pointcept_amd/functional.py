@@ -1230,3 +1230,116 @@ def cluster_agg_torch(us, vs, a: torch.Tensor, gc: "ops.GridClusters") -> torch.
         feats.append(pf.new_zeros((n_c, pf.shape[1])).index_add(0, cl, pf)[cl])
     adp = torch.softmax(a, dim=1)
     return torch.einsum("l n, l n c -> l c", adp, torch.stack(feats, dim=1))
+
+
+# ------------------------------------------------------------------------------------------------
+# PointGroup (point_group_v1m1_base.py:72-91): masked L1 + negative-cosine offset losses, one fused pass each way
+# ------------------------------------------------------------------------------------------------
+class _PGBiasLoss(Function):
+    @staticmethod
+    def forward(ctx, bias_pred, coord, centroid, instance, ignore_index):
+        out = ops.pg_bias_loss_fwd(bias_pred, coord, centroid, instance, ignore_index)
+        ctx.save_for_backward(bias_pred, coord, centroid, instance, out)
+        ctx.ignore_index = ignore_index
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_l1, g_cos):
+        bias_pred, coord, centroid, instance, out = ctx.saved_tensors
+        z = torch.zeros((), dtype=torch.float32, device=bias_pred.device)
+        dout = torch.stack([z if g_l1 is None else g_l1.float().reshape(()), z if g_cos is None else g_cos.float().reshape(())])
+        d = ops.pg_bias_loss_bwd(bias_pred, coord, centroid, instance, ctx.ignore_index, dout, out)
+        return d, None, None, None, None
+
+
+def pg_bias_loss(bias_pred: torch.Tensor, coord: torch.Tensor, centroid: torch.Tensor, instance: torch.Tensor, ignore_index: int = -1):
+    """(bias_l1_loss, bias_cosine_loss) of point_group_v1m1_base.py:72-91 with bias_gt = centroid - coord; fp32 scalars"""
+    return _PGBiasLoss.apply(bias_pred, coord, centroid, instance, int(ignore_index))
+
+
+def pg_bias_loss_torch(bias_pred, coord, centroid, instance, ignore_index: int = -1):
+    """the reference's expression (point_group_v1m1_base.py:72-91), for A/B"""
+    mask = (instance != ignore_index).float()
+    bias_gt = centroid - coord
+    bias_dist = torch.sum(torch.abs(bias_pred - bias_gt), dim=-1)
+    l1 = torch.sum(bias_dist * mask) / (torch.sum(mask) + 1e-8)
+    pn = bias_pred / (torch.norm(bias_pred, p=2, dim=1, keepdim=True) + 1e-8)
+    gn = bias_gt / (torch.norm(bias_gt, p=2, dim=1, keepdim=True) + 1e-8)
+    cos = -(pn * gn).sum(-1)
+    return l1, torch.sum(cos * mask) / (torch.sum(mask) + 1e-8)
+
+
+def pg_ball_query_torch(xyz: torch.Tensor, batch_idxs: torch.Tensor, batch_offsets, radius: float, chunk: int = 256):
+    """ballquery_batch_p as chunked brute-force torch (the A/B baseline and cross-check of csrc/pg_cluster.hip): the reference's
+    unfused d2 < radius^2, ascending neighbours, the first 1000 kept -> (idx int32, start_len int32 [n, 2])"""
+    x = xyz.float().contiguous()
+    n = x.shape[0]
+    off = [int(v) for v in torch.as_tensor(batch_offsets).tolist()]
+    bidx = batch_idxs.long()
+    r2 = float(torch.tensor(radius, dtype=torch.float32) * torch.tensor(radius, dtype=torch.float32))   # fp32 radius * radius
+    lens = torch.zeros(n, dtype=torch.int64, device=x.device)
+    pieces = []
+    for q0 in range(0, n, chunk):
+        q1 = min(n, q0 + chunk)
+        qb = bidx[q0:q1]
+        bs = sorted(set(qb.tolist()))
+        for b in bs:
+            rows = torch.nonzero(qb == b)[:, 0] + q0
+            s, e = off[b], off[b + 1]
+            o, seg = x[rows], x[s:e]
+            dx = o[:, None, 0] - seg[None, :, 0]
+            dy = o[:, None, 1] - seg[None, :, 1]
+            dz = o[:, None, 2] - seg[None, :, 2]
+            d2 = dx * dx + dy * dy
+            d2 = d2 + dz * dz
+            hit = d2 < r2
+            hit &= torch.cumsum(hit.to(torch.int32), dim=1) <= 1000
+            lens[rows] = hit.sum(1)
+            rr, kk = torch.nonzero(hit, as_tuple=True)
+            pieces.append((rows[rr], kk + s))
+    if pieces:
+        rows = torch.cat([p[0] for p in pieces])
+        ks = torch.cat([p[1] for p in pieces])
+        o = torch.argsort(rows * (n + 1) + ks)
+        idx = ks[o].to(torch.int32)
+    else:
+        idx = torch.zeros(0, dtype=torch.int32, device=x.device)
+    starts = torch.cumsum(lens, 0) - lens
+    return idx, torch.stack([starts, lens], 1).to(torch.int32)
+
+
+def pg_bfs_cluster_host(label, idx, start_len, threshold: int):
+    """bfs_cluster.cpp:53-123 on the host (the A/B baseline): CPU int32 tensors, members in BFS order"""
+    from collections import deque
+
+    lab = label.cpu().numpy()
+    ix = idx.cpu().numpy()
+    sl = start_len.cpu().numpy()
+    n = sl.shape[0]
+    visited = bytearray(n)
+    rows, offs = [], [0]
+    for i in range(n):
+        if visited[i]:
+            continue
+        cc = [i]
+        visited[i] = 1
+        q = deque(cc)
+        while q:
+            cur = q.popleft()
+            s, ln, lc = sl[cur, 0], sl[cur, 1], lab[cur]
+            for j in ix[s:s + ln].tolist():
+                if visited[j] or lab[j] != lc:
+                    continue
+                visited[j] = 1
+                cc.append(j)
+                q.append(j)
+        if len(cc) >= threshold:
+            rows.append(cc)
+            offs.append(offs[-1] + len(cc))
+    import numpy as np
+
+    cidx = np.zeros((offs[-1], 2), dtype=np.int32)
+    for k, cc in enumerate(rows):
+        cidx[offs[k]:offs[k + 1], 0] = k
+        cidx[offs[k]:offs[k + 1], 1] = cc
+    return torch.from_numpy(cidx), torch.tensor(offs, dtype=torch.int32)

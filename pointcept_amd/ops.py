@@ -1496,3 +1496,126 @@ def cluster_agg_bwd(us, vs, a, dout: torch.Tensor, state: torch.Tensor, gc: Grid
                                     ctypes.cast(keep[2], V), ctypes.cast(keep[3], V), ptr(da), ptr(ws), wbytes, stream_ptr()),
           "ptc_cluster_agg_bwd")
     return du, dv, da
+
+
+# ------------------------------------------------------------------------------------------------
+# PointGroup clustering and heads (csrc/pg_cluster.hip)
+# ------------------------------------------------------------------------------------------------
+PG_MAX_NEIGHBOURS = 1000
+
+
+def pg_ball_query(xyz: torch.Tensor, batch_idxs: torch.Tensor, n_batch: int, radius: float):
+    """ballquery_batch_p (bfs_cluster_kernel.cu:16-61) -> (idx [nActive] int32, start_len [n, 2] int32, n_truncated).
+    Neighbours in ascending index order, the first 1000 of each point; sized exactly (ONE host read: nActive)."""
+    require_cuda(xyz, batch_idxs)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise PtcoreError(f"pg_ball_query: xyz must be [n, 3], got {tuple(xyz.shape)}")
+    x = xyz.float().contiguous()
+    b = batch_idxs.to(torch.int32).contiguous()
+    n = x.shape[0]
+    if b.numel() != n:
+        raise PtcoreError("pg_ball_query: batch_idxs must have one entry per point")
+    dev = x.device
+    start_len = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    total = torch.empty(2, dtype=torch.int64, device=dev)
+    nbytes = lib().ptc_pg_ball_query_workspace_bytes(n)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_pg_ball_query_count(ptr(x), ptr(b), n, int(n_batch), float(radius), ptr(start_len), ptr(total), ptr(ws), nbytes,
+                                        stream_ptr()), "ptc_pg_ball_query_count")
+    n_active, n_trunc = [int(v) for v in total.tolist()]
+    if n_active >= 1 << 31:
+        raise PtcoreError(f"pg_ball_query: {n_active} neighbour entries exceed the int32 index range")
+    idx = torch.empty(n_active, dtype=torch.int32, device=dev)
+    if n_active == 0:
+        return idx, start_len, n_trunc
+    check(lib().ptc_pg_ball_query_fill(ptr(x), n, float(radius), ptr(start_len), ptr(idx), ptr(ws), nbytes, stream_ptr()),
+          "ptc_pg_ball_query_fill")
+    return idx, start_len, n_trunc
+
+
+def pg_cluster(label: torch.Tensor, idx: torch.Tensor, start_len: torch.Tensor, threshold: int, skip_negative: bool = False):
+    """bfs_cluster (bfs_cluster.cpp:53-145) -> (cluster_idxs [sumNPoint, 2] int32, cluster_offsets [nCluster + 1] int32), on the
+    device; clusters in seed order, members in ascending point order (ONE host read: the two counts).  skip_negative: no cluster
+    is seeded at a point with a negative label."""
+    require_cuda(label, idx, start_len)
+    lab = label.to(torch.int32).contiguous()
+    ix = idx.to(torch.int32).contiguous()
+    sl = start_len.to(torch.int32).contiguous()
+    n = sl.shape[0]
+    if sl.dim() != 2 or sl.shape[1] != 2 or lab.numel() != n:
+        raise PtcoreError("pg_cluster: start_len must be [n, 2] and label [n]")
+    dev = sl.device
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    nbytes = lib().ptc_pg_cluster_workspace_bytes(n)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_pg_cluster_count(ptr(lab), ptr(ix), ptr(sl), n, int(threshold), int(bool(skip_negative)), ptr(counts), ptr(ws), nbytes, stream_ptr()),
+          "ptc_pg_cluster_count")
+    n_cluster, n_sum = [int(v) for v in counts.tolist()]
+    cidx = torch.empty((n_sum, 2), dtype=torch.int32, device=dev)
+    coff = torch.empty(n_cluster + 1, dtype=torch.int32, device=dev)
+    check(lib().ptc_pg_cluster_fill(n, n_cluster, n_sum, ptr(cidx), ptr(coff), ptr(ws), nbytes, stream_ptr()), "ptc_pg_cluster_fill")
+    return cidx, coff
+
+
+def pg_proposal_scores(logits: torch.Tensor, label: torch.Tensor, cluster_idxs: torch.Tensor, cluster_offsets: torch.Tensor,
+                       point_map: Optional[torch.Tensor] = None):
+    """per cluster: (count int32, class = label[seed] int32, mean softmax(logits)[member, class] fp32); members' logit rows are
+    point_map[member] (or member)."""
+    require_cuda(logits, label, cluster_idxs, cluster_offsets)
+    lg = logits.contiguous()
+    if lg.dim() != 2 or lg.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise PtcoreError(f"pg_proposal_scores: logits must be [n, c] fp32 / bf16 / f16, got {tuple(lg.shape)} {lg.dtype}")
+    k = cluster_offsets.numel() - 1
+    dev = lg.device
+    count = torch.empty(k, dtype=torch.int32, device=dev)
+    cls = torch.empty(k, dtype=torch.int32, device=dev)
+    score = torch.empty(k, dtype=torch.float32, device=dev)
+    pm = None if point_map is None else point_map.to(torch.int64).contiguous()
+    check(lib().ptc_pg_proposal_scores(ptr(lg), dtype_code(lg), lg.shape[0], lg.shape[1], ptr(label.to(torch.int32).contiguous()),
+                                       ptr(cluster_idxs.contiguous()), ptr(cluster_offsets.contiguous()), k, ptr(pm), ptr(count), ptr(cls),
+                                       ptr(score), stream_ptr()), "ptc_pg_proposal_scores")
+    return count, cls, score
+
+
+def pg_proposal_masks(cluster_idxs: torch.Tensor, row: torch.Tensor, n_rows: int, n_points: int, point_map: Optional[torch.Tensor] = None):
+    """dense [n_rows, n_points] int32 masks: 1 at (row[cluster], point_map[point]) for every member of a cluster with row >= 0"""
+    require_cuda(cluster_idxs, row)
+    out = torch.empty((int(n_rows), int(n_points)), dtype=torch.int32, device=cluster_idxs.device)
+    pm = None if point_map is None else point_map.to(torch.int64).contiguous()
+    ci = cluster_idxs.contiguous()
+    check(lib().ptc_pg_proposal_masks(ptr(ci), ci.shape[0], ptr(row.to(torch.int64).contiguous()), ptr(pm), int(n_points), int(n_rows),
+                                      ptr(out), stream_ptr()), "ptc_pg_proposal_masks")
+    return out
+
+
+def _pg_bias_args(bias_pred, coord, centroid, instance):
+    require_cuda(bias_pred, coord, centroid, instance)
+    if bias_pred.dim() != 2 or bias_pred.shape[1] != 3 or bias_pred.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise PtcoreError(f"pg_bias_loss: bias_pred must be [n, 3] fp32 / bf16 / f16, got {tuple(bias_pred.shape)} {bias_pred.dtype}")
+    n = bias_pred.shape[0]
+    c = coord.float().contiguous()
+    g = centroid.float().contiguous()
+    i = instance.to(torch.int64).contiguous()
+    if c.shape != (n, 3) or g.shape != (n, 3) or i.numel() != n:
+        raise PtcoreError("pg_bias_loss: coord / instance_centroid must be [n, 3] and instance [n]")
+    return bias_pred.contiguous(), c, g, i, n
+
+
+def pg_bias_loss_fwd(bias_pred, coord, centroid, instance, ignore_index: int) -> torch.Tensor:
+    """-> [3] fp32: (bias_l1_loss, bias_cosine_loss, sum(mask)) of point_group_v1m1_base.py:72-91"""
+    bp, c, g, i, n = _pg_bias_args(bias_pred, coord, centroid, instance)
+    out = torch.empty(3, dtype=torch.float32, device=bp.device)
+    nbytes = lib().ptc_pg_bias_loss_workspace_bytes(n)
+    ws = _ws(nbytes, bp.device)
+    check(lib().ptc_pg_bias_loss_fwd(ptr(bp), dtype_code(bp), ptr(c), ptr(g), ptr(i), n, int(ignore_index), ptr(out), ptr(ws), nbytes,
+                                     stream_ptr()), "ptc_pg_bias_loss_fwd")
+    return out
+
+
+def pg_bias_loss_bwd(bias_pred, coord, centroid, instance, ignore_index: int, dout: torch.Tensor, fwd_out: torch.Tensor) -> torch.Tensor:
+    """d bias_pred [n, 3] (bias_pred's dtype) from dout [2] fp32 = (d l1, d cos)"""
+    bp, c, g, i, n = _pg_bias_args(bias_pred, coord, centroid, instance)
+    d = torch.empty_like(bp)
+    check(lib().ptc_pg_bias_loss_bwd(ptr(bp), dtype_code(bp), ptr(c), ptr(g), ptr(i), n, int(ignore_index),
+                                     ptr(dout.float().contiguous()), ptr(fwd_out), ptr(d), stream_ptr()), "ptc_pg_bias_loss_bwd")
+    return d

@@ -131,3 +131,77 @@ def to_torch(batch, device):
     import torch
 
     return {k: torch.from_numpy(v).to(device) for k, v in batch.items()}
+
+
+def instance_parse(coord, segment, instance, segment_ignore_index=(-1, 0, 1), instance_ignore_index=-1):
+    """InstanceParser (pointcept/datasets/transform.py:1312-1355): instance ids renumbered over the non-ignored classes,
+    instance_centroid [N, 3] (the instance's mean coordinate, -1 elsewhere) and bbox [K, 8] (centre, size, theta 0, class shifted
+    past the vacated ignore classes)."""
+    instance = instance.copy()
+    mask = ~np.isin(segment, segment_ignore_index)
+    instance[~mask] = instance_ignore_index
+    unique, inverse = np.unique(instance[mask], return_inverse=True)
+    instance[mask] = inverse
+    centroid = np.ones((coord.shape[0], 3)) * instance_ignore_index
+    bbox = np.ones((len(unique), 8)) * instance_ignore_index
+    vacancy = [index for index in segment_ignore_index if index >= 0]
+    for k in range(len(unique)):
+        m = instance == k
+        c = coord[m]
+        cls = np.array([segment[m][0]], dtype=c.dtype)
+        cls -= np.greater(cls, vacancy).sum()
+        centroid[m] = c.mean(0)
+        bbox[k] = np.concatenate([(c.max(0) + c.min(0)) / 2, c.max(0) - c.min(0), np.zeros(1, dtype=c.dtype), cls])
+    return instance, centroid.astype(np.float32), bbox.astype(np.float32)
+
+
+def indoor_instance_scene(seed: int, point_max: int = 102400, grid: float = 0.02, density: int = 12000, n_boxes: int = 14):
+    """indoor_scene's room for instance segmentation: floor = class 0, walls = class 1, each box one instance of a class in [2, 20);
+    adds instance, instance_centroid and bbox as InstanceParser computes them (classes 0 / 1 and -1 ignored)."""
+    rng = np.random.default_rng(seed)
+    L, W, H = 7.0, 5.0, 2.8
+    walls = [([0, 0, 0], [L, 0, 0], [0, W, 0], [0, 0, 1]), ([0, 0, 0], [L, 0, 0], [0, 0, H], [0, 1, 0]),
+             ([0, W, 0], [L, 0, 0], [0, 0, H], [0, -1, 0]), ([0, 0, 0], [0, W, 0], [0, 0, H], [1, 0, 0]),
+             ([L, 0, 0], [0, W, 0], [0, 0, H], [-1, 0, 0])]
+    P, Nr, S, I = [], [], [], []
+    for k, (o, u, v, nv) in enumerate(walls):
+        a = np.linalg.norm(u) * np.linalg.norm(v)
+        p = _rect(rng, o, u, v, int(a * density))
+        P.append(p)
+        Nr.append(np.tile(np.asarray(nv, float), (p.shape[0], 1)))
+        S.append(np.full(p.shape[0], 0 if k == 0 else 1))
+        I.append(np.full(p.shape[0], -1))
+    for b in range(n_boxes):
+        s = rng.uniform(0.3, 1.6, 3)
+        bp, bn = _box(rng, [rng.uniform(0.8, L - 0.8), rng.uniform(0.8, W - 0.8), s[2] / 2], s, int(density * 1.2))
+        P.append(bp)
+        Nr.append(bn)
+        S.append(np.full(bp.shape[0], int(rng.integers(2, 20))))
+        I.append(np.full(bp.shape[0], b))
+    p, nrm, seg, ins = np.concatenate(P), np.concatenate(Nr), np.concatenate(S), np.concatenate(I)
+    gc = np.floor(p / grid).astype(np.int64)
+    gc -= gc.min(0)
+    key = (gc[:, 0] * 4096 + gc[:, 1]) * 4096 + gc[:, 2]
+    _, first = np.unique(key, return_index=True)
+    if first.shape[0] > point_max:
+        centre = gc[first[rng.integers(first.shape[0])]]
+        d2 = ((gc[first] - centre) ** 2).sum(1)
+        first = first[np.argpartition(d2, point_max)[:point_max]]
+    first = first[rng.permutation(first.shape[0])]      # dataloader order
+    gc, nrm, seg, ins = gc[first], nrm[first], seg[first], ins[first]
+    gc = gc - gc.min(0)
+    n = gc.shape[0]
+    coord = ((gc + 0.5) * grid).astype(np.float32)
+    feat = np.concatenate([rng.random((n, 3)).astype(np.float32), nrm.astype(np.float32)], axis=1)
+    segment = seg.astype(np.int64)
+    instance, centroid, bbox = instance_parse(coord, segment, ins.astype(np.int64))
+    return dict(coord=coord, grid_coord=gc.astype(np.int64), feat=feat, segment=segment, instance=instance.astype(np.int64),
+                instance_centroid=centroid, bbox=bbox)
+
+
+def indoor_instance_batch(seeds, sizes):
+    """collated indoor_instance_scene batch (the per-scene bbox tables dropped: they are not per-point)"""
+    scenes = [indoor_instance_scene(s, n) for s, n in zip(seeds, sizes)]
+    for sc in scenes:
+        sc.pop("bbox")
+    return collate(scenes)
