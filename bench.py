@@ -17,15 +17,22 @@ and refuses to report anything but n_gpus = N.
 Inputs are generated on the host, copied to HBM BEFORE the timed region and reused every step
 (rulebooks, sort, pad maps are rebuilt every step -- nothing is cached across steps).
 
-Prints ONE JSON line on rank 0 (contract of the driver) carrying
+Prints ONE JSON line on rank 0 (contract of the driver).  A plain run does only what that line's headline needs: it sets up,
+warms up, times --steps steps, writes --dump-outputs if asked and prints metric / value / unit / ms_per_step / dtype / config.
+--full adds, after the timed steps (none of it changes the headline or the dumped arrays):
+  step_traffic    : HBM bytes of one step, read from the latest committed profiles/*_step_traffic.txt (not measured here)
   roofline        : the dominant kernel (serialized attention forward at the dec0/enc0 shapes),
                     timed live with HIP events on the launch stream
   roofline_gather : the gather-table convolution (CPE conv 64->64 at stage 0), HBM-bound by SURVEY 8(d)
   roofline_gemm   : the Linear layers of a stage-3 Block (256 channels, ~20000 rows: qkv, fc1 + GELU, fc2 and the five weight gradients),
                     MFMA-bound by SURVEY 8(d): gemm3.h / wgrad3.h against the bf16 matrix peak
-  secondary       : BASELINE configs[1] (SpUNet-v1m1, 8 x 100000 voxels) measured in the same process
+  secondary       : BASELINE configs[1] (SpUNet-v1m1, 8 x 100000 voxels) measured in the same process, with its fp16 recipe;
+                    secondary_outdoor (configs[4]) and secondary_f2 (PT-v3m2 at the Sonata widths) after it
+  recipe_fp16     : the headline step under fp16 autocast + GradScaler, measured by a child process
   cpu_baseline    : the CPU oracle (oracle/ptv3_model.py, port of the reference model) timed on this
                     box's host cores on a bounded sample (rank 0, N=1 only)
+  per_rank_ms_per_step, ms_per_step_without_gradient_exchange : N > 1 only, every rank's own step time and the step without DDP's all-reduce
+(--no-secondary, --no-cpu-baseline and --no-fp16-recipe drop parts of that set.)
 
 --dump-outputs DIR writes what the last timed step computed (loss, logits, gradients, updated parameters; fixed seeded
 samples of the large ones) as DIR/*.npy, so that two builds run with the same arguments can be compared output for output.
@@ -65,6 +72,9 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8, help="scenes per GPU")
     ap.add_argument("--points", type=int, default=102400, help="voxels per scene")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also measure the rooflines, the secondary workloads, the fp16 recipe, the CPU baseline and "
+                         "the multi-GPU diagnostics (a plain run measures the headline only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the SpUNet (configs[1]) measurement and the gather roofline")
     ap.add_argument("--ce-only", action="store_true", help="criteria = CrossEntropy only (default: CE + Lovasz-Softmax, the config's criteria)")
@@ -624,10 +634,10 @@ def main():
         hook.remove()
         if rank == 0:
             dumped = dump_outputs(args.dump_outputs, loss, seen.pop("logits"), model)
-    # multi-GPU diagnostics (outside the timed region): every rank's own step time, and the same K steps WITHOUT the gradient exchange
-    # (DDP.no_sync) -- the difference is the all-reduce time the overlap with backward did not hide
+    # multi-GPU diagnostics (--full, outside the timed region): every rank's own step time, and the same K steps WITHOUT the gradient
+    # exchange (DDP.no_sync) -- the difference is the all-reduce time the overlap with backward did not hide
     per_rank_ms, ms_no_sync = None, None
-    if world > 1 and torch.distributed.is_initialized():
+    if args.full and world > 1 and torch.distributed.is_initialized():
         t = torch.tensor([dt / args.steps * 1e3], dtype=torch.float64, device=device)
         allt = [torch.zeros_like(t) for _ in range(world)]
         t0 = time.perf_counter()
@@ -664,14 +674,17 @@ def main():
         }
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if world > 1:
+            out["cpu_affinity_rank0"] = affinity
         if per_rank_ms is not None:
             out["per_rank_ms_per_step"] = per_rank_ms
-            out["cpu_affinity_rank0"] = affinity
             out["ms_per_step_without_gradient_exchange"] = ms_no_sync
             out["exposed_allreduce_ms_per_step"] = None if ms_no_sync is None else round(out["ms_per_step"] - ms_no_sync, 3)
         if not args.stub and args.model == "ptv3":
             out["config"]["points_per_gpu"] = int(batch["offset"][-1])
             out["config"]["loss"] = "CrossEntropy(ignore_index=-1)" + ("" if args.ce_only else " + LovaszSoftmax")
+        # everything below is --full: diagnostics measured after the headline, each in its own try so that none can take the line with it
+        if args.full and not args.stub and args.model == "ptv3":
             if args.batch == 8 and args.points == 102400:      # the table was measured on the default workload
                 st = step_traffic()
                 if st:
@@ -690,7 +703,7 @@ def main():
                     out["roofline_gemm"] = gemm_roofline(device)
                 except Exception as e:
                     out["roofline_gemm"] = {"error": repr(e)}
-        if not args.stub and args.model == "ptv3" and world == 1 and not args.no_secondary:
+        if args.full and not args.stub and args.model == "ptv3" and world == 1 and not args.no_secondary:
             try:
                 del step, step_model, model, opt, batch
                 torch.cuda.empty_cache()
@@ -719,7 +732,7 @@ def main():
                 del st2, m2, o2, b2
             except Exception as e:
                 out["secondary"] = {"error": repr(e)}
-        if not args.stub and args.model == "ptv3" and world == 1 and not args.no_secondary:
+        if args.full and not args.stub and args.model == "ptv3" and world == 1 and not args.no_secondary:
             try:      # BASELINE configs[4] (outdoor LiDAR, ~200k voxels per scene, depth-12 grid) on this one GPU
                 torch.cuda.empty_cache()
                 torch.manual_seed(1234)
@@ -737,7 +750,7 @@ def main():
                 torch.cuda.empty_cache()
             except Exception as e:
                 out["secondary_outdoor"] = {"error": repr(e)}
-        if not args.stub and args.model == "ptv3" and world == 1 and not args.no_secondary:
+        if args.full and not args.stub and args.model == "ptv3" and world == 1 and not args.no_secondary:
             try:      # SURVEY 8(f).2 at the widths the reference ships: PT-v3m2 with configs/sonata's channel plan on the bench batch
                 torch.cuda.empty_cache()
                 torch.manual_seed(1234)
@@ -754,9 +767,9 @@ def main():
                 torch.cuda.empty_cache()
             except Exception as e:
                 out["secondary_f2"] = {"error": repr(e)}
-        if not args.stub and args.model == "ptv3" and world == 1 and amp == "bf16" and not args.no_secondary and not args.no_fp16_recipe:
+        if args.full and not args.stub and args.model == "ptv3" and world == 1 and amp == "bf16" and not args.no_secondary and not args.no_fp16_recipe:
             out["recipe_fp16"] = fp16_recipe_in_a_child(args)
-        if not args.stub and args.model == "ptv3" and world == 1 and not args.no_cpu_baseline:
+        if args.full and not args.stub and args.model == "ptv3" and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.cpu_sample_points, args.points, args.cpu_iters, not args.ce_only)
             except Exception as e:

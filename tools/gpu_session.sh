@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU-box session.  Usage (through gpurun): bash tools/gpu_session.sh <tag> <sections...>
 #   tests      whole -m gpu suite            ops     tools/bench_ops.py
-#   bench      bench.py (default switches)   ab:<ENV=V,...>  bench.py with switches (no cpu baseline)
+#   bench      bench.py --full               ab:<ENV=V,...>  bench.py headline with switches
 #   prof       rocprofv3 kernel stats of ONE steady-state bench.py step (two runs, tools/steady_state_stats.py); profsmall: the 2 x 20000 step
 #   contention tools/host_contention.py: host CPU time per step of 1 vs 8 concurrent processes
 #   hostlead   tools/host_lead.py: host enqueue time per step vs completed time (executor on / off, and a 2 x 20000-voxel step)
@@ -32,7 +32,7 @@ for sec in "$@"; do
     w7) timeout 600 python tools/wgrad7_time.py > $O/${TAG}_wgrad7_time.txt 2>&1; cat $O/${TAG}_wgrad7_time.txt;;
     w7prof) cd /tmp; timeout 600 rocprofv3 --kernel-trace --stats -d $O/${TAG}_w7prof -- python $R/tools/wgrad7_time.py > $O/${TAG}_w7prof.log 2>&1
           cd $R; TOP=12 python tools/prof_top.py $O/${TAG}_w7prof 1 $O/${TAG}_wgrad7_kernel_stats.csv > $O/${TAG}_w7prof_top.log 2>&1; rm -rf $O/${TAG}_w7prof; head -14 $O/${TAG}_wgrad7_kernel_stats.csv | cut -c1-150;;
-    bench) timeout 900 python bench.py --steps 10 --warmup 3 > $O/${TAG}_bench.log 2>&1; echo "bench rc=$?" >> $O/${TAG}_env.log; tail -1 $O/${TAG}_bench.log | cut -c1-330;;
+    bench) timeout 900 python bench.py --full --steps 10 --warmup 3 > $O/${TAG}_bench.log 2>&1; echo "bench rc=$?" >> $O/${TAG}_env.log; tail -1 $O/${TAG}_bench.log | cut -c1-330;;
     hostlead) timeout 600 python tools/host_lead.py > $O/${TAG}_host_lead.txt 2>&1; PTC_EXEC_BLOCK=0 timeout 600 python tools/host_lead.py >> $O/${TAG}_host_lead.txt 2>&1; timeout 600 python tools/host_lead.py --scenes 2 --points 20000 >> $O/${TAG}_host_lead.txt 2>&1; cat $O/${TAG}_host_lead.txt;;
     contention) timeout 900 python tools/host_contention.py > $O/${TAG}_host_contention.txt 2>&1; cat $O/${TAG}_host_contention.txt;;
     smoke) timeout 600 python __graft_entry__.py --smoke > $O/${TAG}_smoke.log 2>&1; echo "smoke rc=$?" >> $O/${TAG}_env.log; tail -2 $O/${TAG}_smoke.log;;
