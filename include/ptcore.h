@@ -803,6 +803,48 @@ int ptc_pg_bias_loss_fwd(const void* bias_pred, int dtype, const float* coord, c
 int ptc_pg_bias_loss_bwd(const void* bias_pred, int dtype, const float* coord, const float* centroid, const int64_t* instance, int64_t n,
                          int64_t ignore_index, const float* dout, const float* fwd_out, void* dbias_pred, ptc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * S. Masked Scene Contrast pretraining (pointcept/models/masked_scene_contrast/masked_scene_contrast_v1m1_base.py:69-203),
+ *    csrc/msc.hip.  No float atomics anywhere; every result is bit-reproducible.
+ * ptc_msc_match: for each query new_xyz[q] (view 1) the up-to-k (k <= 8) points of the same scene of xyz (view 2) with fp32
+ *   sqrt(d2) < max_radius, ascending (d2, index) -- identical to ptc_knn_query(k) followed by `dist < max_radius`.  count [m] int32,
+ *   cand [m,k] int32 (-1 padding), stats [2] int32 on the device: (queries with count > 0, largest count).  A non-finite coordinate
+ *   matches nothing; m == 0, n == 0 and max_radius <= 0 give empty results.
+ * ptc_msc_select: match_index [n_matched,2] int64 = (q, cand[q][count[q] - 1 - r[j] % count[q]]) for the j-th matched query q in
+ *   ascending order (:154-169); r [n_matched] int64.
+ * ptc_msc_patch_rank: cell1 [n1,3] / cell2 [n2,3] fp32 hold floor(origin_coord / mask_grid_size) of the two views, offset1 / offset2
+ *   [b] int32 their scene ends.  cluster [n1 + n2] int32 (view 1 first) = rank, in ascending signed order, of the id
+ *   voxel_grid(pos = cell, size = 1, batch, start = 0) gives the point over the union of both views (num = trunc(max) + 1 per axis;
+ *   negative cells collide as they do there); patch_num [1] int64 on the device.  Coordinates must be finite.
+ * ptc_msc_patch_masks: mask1 [n1] / mask2 [n2] uint8 = (patch_mask[cluster] == 1) / (== 2); patch_mask [patch_num] int32.
+ * ptc_msc_nce_fwd: A = rows match_index[:,0] of feat1 [n1,c], B = rows match_index[:,1] of feat2 [n2,c] (fp32, c a multiple of 4,
+ *   <= 256; 1 <= p <= 2^20), each normalised x / (|x| + 1e-7); S = A B^T is formed tile by tile (exact-fp32 MFMA) and never stored.
+ *   out [3] = (mean_i(lse_i(S / nce_t) - S_ii / nce_t), mean_i S_ii, mean(S) - out[1] / p).  Saved for the backward: an, bn [p,c],
+ *   na, nb [p] (the norms), lse [p].  An index outside its feature matrix gives a zero row and no gradient.
+ * ptc_msc_nce_bwd: dfeat1 [n1,c] / dfeat2 [n2,c]: the rows named by match_index are WRITTEN (callers pass zeros) with
+ *   d out[0] * dloss[0] (dloss on the device); rows named several times are summed in ascending pair order.
+ *   Both use a workspace of ptc_msc_nce_workspace_bytes(p, c) = O(p c).
+ * ------------------------------------------------------------------------------------------ */
+size_t ptc_msc_match_workspace_bytes(int64_t n);
+int ptc_msc_match(const float* xyz, const int32_t* offset, const float* new_xyz, const int32_t* new_offset, int b, int64_t n, int64_t m,
+                  int k, float max_radius, int32_t* count, int32_t* cand, int32_t* stats, void* workspace, size_t workspace_bytes,
+                  ptc_stream_t stream);
+size_t ptc_msc_select_workspace_bytes(int64_t m);
+int ptc_msc_select(const int32_t* count, const int32_t* cand, int64_t m, int k, const int64_t* r, int64_t n_matched,
+                   int64_t* match_index, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+size_t ptc_msc_patch_workspace_bytes(int64_t n_total);
+int ptc_msc_patch_rank(const float* cell1, const int32_t* offset1, int64_t n1, const float* cell2, const int32_t* offset2, int64_t n2,
+                       int b, int32_t* cluster, int64_t* patch_num, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+int ptc_msc_patch_masks(const int32_t* cluster, const int32_t* patch_mask, int64_t patch_num, int64_t n1, int64_t n2, uint8_t* mask1,
+                        uint8_t* mask2, ptc_stream_t stream);
+size_t ptc_msc_nce_workspace_bytes(int64_t p, int c);
+int ptc_msc_nce_fwd(const float* feat1, int64_t n1, const float* feat2, int64_t n2, const int64_t* match_index, int64_t p, int c,
+                    float nce_t, float* an, float* bn, float* na, float* nb, float* lse, float* out, void* workspace,
+                    size_t workspace_bytes, ptc_stream_t stream);
+int ptc_msc_nce_bwd(const float* an, const float* bn, const float* na, const float* nb, const float* lse, const int64_t* match_index,
+                    int64_t p, int c, int64_t n1, int64_t n2, float nce_t, const float* dloss, float* dfeat1, float* dfeat2,
+                    void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,18 @@ _SIGNATURES = {
     "ptc_pg_bias_loss_workspace_bytes": (c_size, [c_i64]),
     "ptc_pg_bias_loss_fwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
     "ptc_pg_bias_loss_bwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "ptc_msc_match_workspace_bytes": (c_size, [c_i64]),
+    "ptc_msc_match": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_msc_select_workspace_bytes": (c_size, [c_i64]),
+    "ptc_msc_select": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_msc_patch_workspace_bytes": (c_size, [c_i64]),
+    "ptc_msc_patch_rank": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_msc_patch_masks": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
+    "ptc_msc_nce_workspace_bytes": (c_size, [c_i64, c_int]),
+    "ptc_msc_nce_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                c_size, c_ptr]),
+    "ptc_msc_nce_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_i64, c_i64, c_f32, c_ptr, c_ptr, c_ptr, c_ptr,
+                                c_size, c_ptr]),
     "ptc_lovasz_softmax_workspace_bytes": (c_size, [c_i64, c_int]),
     "ptc_lovasz_softmax": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
 }

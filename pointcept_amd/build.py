@@ -52,6 +52,7 @@ HIP_SOURCES = [
     "mlp.hip",
     "cluster_agg.hip",
     "pg_cluster.hip",
+    "msc.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

@@ -78,14 +78,34 @@ OPT_IN_MODEL_CLASSES = {
     "OACNNs": ("oacnns", "OACNNs"),                                   # oacnns_v1m1_base.py:212
     "PG-v1m1": ("point_group", "PointGroup"),                         # point_group_v1m1_base.py:22
     "PG-v1m2": ("point_group", "PointGroupV1m2"),                     # point_group_v1m2_custom_criteria.py:25
+    "MSC-v1m1": ("masked_scene_contrast", "MaskedSceneContrast"),     # masked_scene_contrast_v1m1_base.py:24
 }
+
+
+def build_backbone(cfg):
+    """an engine backbone from a config dict (its `type` one of compat.MODEL_CLASSES / OPT_IN_MODEL_CLASSES), else the
+    reference's registry (inside a Pointcept checkout); a module is taken as is"""
+    import importlib
+
+    import torch.nn as nn
+
+    if isinstance(cfg, nn.Module):
+        return cfg
+    kw = dict(cfg)
+    name = kw.pop("type")
+    if name in MODEL_CLASSES or name in OPT_IN_MODEL_CLASSES:
+        mod, cls = MODEL_CLASSES.get(name) or OPT_IN_MODEL_CLASSES[name]
+        return getattr(importlib.import_module(f"{__package__}.{mod}"), cls)(**kw)
+    from pointcept.models.builder import build_model
+
+    return build_model(cfg)
 
 
 def register_models(registry, names=None, force: bool = True) -> list:
     """Registers the engine's module-level ports in the reference's `MODELS` registry (pointcept/models/builder.py) under the
     names the reference's configs use, replacing the CUDA-library implementations (`force=True`), so that
     `MODELS.build(cfg.model.backbone)` constructs them.  Returns the names registered.  Without `names`: every name of
-    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs, PointGroup) only when named.
+    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs, PointGroup, MSC) only when named.
 
         from pointcept.models.builder import MODELS
         import pointcept_amd.compat; pointcept_amd.compat.register_models(MODELS)

@@ -1343,3 +1343,64 @@ def pg_bfs_cluster_host(label, idx, start_len, threshold: int):
         cidx[offs[k]:offs[k + 1], 0] = k
         cidx[offs[k]:offs[k + 1], 1] = cc
     return torch.from_numpy(cidx), torch.tensor(offs, dtype=torch.int32)
+
+
+# ------------------------------------------------------------------------------------------------
+# Masked Scene Contrast (masked_scene_contrast_v1m1_base.py:144-203): matching and the fused InfoNCE loss
+# ------------------------------------------------------------------------------------------------
+class _MSCNce(Function):
+    @staticmethod
+    def forward(ctx, feat1, feat2, match_index, nce_t):
+        out, state = ops.msc_nce_fwd(feat1, feat2, match_index, nce_t)
+        ctx.save_for_backward(*state)
+        ctx.shape = (feat1.shape[0], feat2.shape[0], float(nce_t))
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, g_loss, g_pos, g_neg):
+        n1, n2, nce_t = ctx.shape
+        if g_loss is None:
+            return None, None, None, None
+        d1, d2 = ops.msc_nce_bwd(tuple(ctx.saved_tensors), n1, n2, nce_t, g_loss)
+        return d1, d2, None, None
+
+
+def msc_nce(feat1: torch.Tensor, feat2: torch.Tensor, match_index: torch.Tensor, nce_t: float):
+    """(nce loss, pos_sim, neg_sim) of compute_contrastive_loss (:179-193) on the fused kernels: fp32 scalars, the loss
+    differentiable in feat1 / feat2, the two similarities detached as there.  16-bit features are cast up (the config's recipe is
+    fp32, enable_amp = False)."""
+    with torch.autocast(device_type=feat1.device.type, enabled=False):
+        loss, pos, neg = _MSCNce.apply(feat1.float(), feat2.float(), match_index, float(nce_t))
+    return loss, pos.detach(), neg.detach()
+
+
+def msc_nce_torch(feat1, feat2, match_index, nce_t: float):
+    """the reference's expression (:179-193): gather, normalise, the dense P x P similarity matrix, CrossEntropy (A/B and CPU path)"""
+    a = feat1[match_index[:, 0]]
+    b = feat2[match_index[:, 1]]
+    a = a / (torch.norm(a, p=2, dim=1, keepdim=True) + 1e-7)
+    b = b / (torch.norm(b, p=2, dim=1, keepdim=True) + 1e-7)
+    sim = torch.mm(a, b.transpose(1, 0))
+    with torch.no_grad():
+        pos_sim = torch.diagonal(sim).mean()
+        neg_sim = sim.mean(dim=-1).mean() - pos_sim / match_index.shape[0]
+    labels = torch.arange(sim.shape[0], device=a.device).long()
+    loss = torch.nn.functional.cross_entropy(torch.div(sim, nce_t), labels, reduction="mean")
+    return loss, pos_sim, neg_sim
+
+
+def msc_candidates_torch(k: int, max_radius: float, xyz, offset, new_xyz, new_offset):
+    """(count, cand) of ops.msc_match written as the reference writes it: knn_query, then `distance < max_radius` (:147-162)"""
+    idx, dist = ops.knn_query(k, xyz.float(), offset.int(), new_xyz.float(), new_offset.int())
+    keep = dist < max_radius
+    return keep.sum(1).to(torch.int32), torch.where(keep, idx, torch.full_like(idx, -1))
+
+
+def msc_select_torch(count: torch.Tensor, cand: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """:154-169 on (count, cand): the compacted (query, candidate) list, unique's counts, cumsum(count) - r % count - 1"""
+    k = cand.shape[1]
+    index = torch.cat([torch.arange(cand.shape[0], device=cand.device, dtype=torch.long).view(-1, 1, 1).expand(-1, k, 1),
+                       cand.long().view(-1, k, 1)], dim=-1)[cand >= 0]
+    _, cnt = index[:, 0].unique(return_counts=True)
+    select = torch.cumsum(cnt, dim=0) - r.to(cnt.device) % cnt - 1
+    return index[select]

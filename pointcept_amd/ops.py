@@ -1619,3 +1619,145 @@ def pg_bias_loss_bwd(bias_pred, coord, centroid, instance, ignore_index: int, do
     check(lib().ptc_pg_bias_loss_bwd(ptr(bp), dtype_code(bp), ptr(c), ptr(g), ptr(i), n, int(ignore_index),
                                      ptr(dout.float().contiguous()), ptr(fwd_out), ptr(d), stream_ptr()), "ptc_pg_bias_loss_bwd")
     return d
+
+
+# ------------------------------------------------------------------------------------------------
+# Masked Scene Contrast (csrc/msc.hip)
+# ------------------------------------------------------------------------------------------------
+MSC_MAX_K = 8
+
+
+def _msc_offsets(offset, new_offset, what):
+    off, noff = offset.to(torch.int32).contiguous(), new_offset.to(torch.int32).contiguous()
+    if off.numel() != noff.numel() or off.numel() == 0:
+        raise PtcoreError(f"{what}: both views must list the same (non-zero) number of scenes")
+    return off, noff
+
+
+def msc_match(k: int, max_radius: float, xyz, offset, new_xyz, new_offset):
+    """For each row of new_xyz (view 1) the up-to-k points of its scene of xyz (view 2) with fp32 sqrt(d2) < max_radius, ascending
+    (distance, index): knn_query(k, ...) followed by `dist < max_radius` (masked_scene_contrast_v1m1_base.py:147-162), found in the
+    27 grid cells around the query.  -> (count [m] int32, cand [m, k] int32 with -1 padding, stats [2] int32 on the device:
+    matched queries, largest count).  No host read."""
+    require_cuda(xyz, offset, new_xyz, new_offset)
+    x, q = _xyz(xyz, "xyz"), _xyz(new_xyz, "new_xyz")
+    off, noff = _msc_offsets(offset, new_offset, "msc_match")
+    if not 1 <= int(k) <= MSC_MAX_K:
+        raise PtcoreError(f"msc_match: k={k} not in [1, {MSC_MAX_K}]")
+    n, m, dev = x.shape[0], q.shape[0], q.device
+    count = torch.empty(m, dtype=torch.int32, device=dev)
+    cand = torch.empty((m, int(k)), dtype=torch.int32, device=dev)
+    stats = torch.empty(2, dtype=torch.int32, device=dev)
+    nbytes = lib().ptc_msc_match_workspace_bytes(n)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_msc_match(ptr(x), ptr(off), ptr(q), ptr(noff), off.numel(), n, m, int(k), float(max_radius), ptr(count), ptr(cand),
+                              ptr(stats), ptr(ws), nbytes, stream_ptr()), "ptc_msc_match")
+    return count, cand, stats
+
+
+def msc_select(count: torch.Tensor, cand: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """match_index [len(r), 2] int64 of :154-169: the j-th matched query q (ascending) with candidate count[q] - 1 - r[j] % count[q];
+    len(r) must be the number of matched queries (stats[0] of msc_match)."""
+    require_cuda(count, cand, r)
+    cnt, cd = count.to(torch.int32).contiguous(), cand.to(torch.int32).contiguous()
+    rr = r.to(torch.int64).contiguous()
+    m, k = cd.shape
+    if cnt.numel() != m or rr.dim() != 1:
+        raise PtcoreError("msc_select: count must be [m], cand [m, k] and r [n_matched]")
+    out = torch.empty((rr.numel(), 2), dtype=torch.int64, device=cd.device)
+    nbytes = lib().ptc_msc_select_workspace_bytes(m)
+    ws = _ws(nbytes, cd.device)
+    check(lib().ptc_msc_select(ptr(cnt), ptr(cd), m, k, ptr(rr), rr.numel(), ptr(out), ptr(ws), nbytes, stream_ptr()), "ptc_msc_select")
+    return out
+
+
+def msc_patch_rank(cell1, offset1, cell2, offset2):
+    """cell1 / cell2 [n, 3] fp32 = floor(origin_coord / mask_grid_size) of the two views -> (cluster [n1 + n2] int32, view 1 first:
+    the rank of each point's voxel_grid(pos=cell, size=1, batch, start=0) id over the union of both views in torch.unique's sorted
+    order; patch_num [1] int64 on the device)."""
+    require_cuda(cell1, offset1, cell2, offset2)
+    c1, c2 = _xyz(cell1, "cell1"), _xyz(cell2, "cell2")
+    o1, o2 = _msc_offsets(offset1, offset2, "msc_patch_rank")
+    n1, n2, dev = c1.shape[0], c2.shape[0], c1.device
+    cluster = torch.empty(n1 + n2, dtype=torch.int32, device=dev)
+    patch_num = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = lib().ptc_msc_patch_workspace_bytes(n1 + n2)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_msc_patch_rank(ptr(c1), ptr(o1), n1, ptr(c2), ptr(o2), n2, o1.numel(), ptr(cluster), ptr(patch_num), ptr(ws), nbytes,
+                                   stream_ptr()), "ptc_msc_patch_rank")
+    return cluster, patch_num
+
+
+def msc_patch_masks(cluster: torch.Tensor, patch_mask: torch.Tensor, n1: int):
+    """(view1_point_mask [n1] bool, view2_point_mask bool) = (patch_mask[cluster] == 1, == 2) of :118-140"""
+    require_cuda(cluster, patch_mask)
+    cl, pm = cluster.to(torch.int32).contiguous(), patch_mask.to(torch.int32).contiguous()
+    n2 = cl.numel() - int(n1)
+    if n2 < 0:
+        raise PtcoreError("msc_patch_masks: n1 exceeds the number of points")
+    m1 = torch.empty(int(n1), dtype=torch.uint8, device=cl.device)
+    m2 = torch.empty(n2, dtype=torch.uint8, device=cl.device)
+    check(lib().ptc_msc_patch_masks(ptr(cl), ptr(pm), pm.numel(), int(n1), n2, ptr(m1), ptr(m2), stream_ptr()), "ptc_msc_patch_masks")
+    return m1.view(torch.bool), m2.view(torch.bool)
+
+
+def msc_cross_masks(view1_origin_coord, view1_offset, view2_origin_coord, view2_offset, mask_grid_size: float, mask_rate: float,
+                    rand_perm=None):
+    """generate_cross_masks (:69-141) -> (view1_point_mask, view2_point_mask) bool.  The patches are the voxel_grid ids of
+    floor(origin / mask_grid_size) over the union of both views, ranked as torch.unique ranks them; rand_perm(patch_num) -> the
+    permutation of the patches (default torch.randperm, as there).  ONE host read (patch_num); no [patch_num, patch_max_point] map."""
+    if not mask_rate <= 0.5:
+        raise PtcoreError("msc_cross_masks: mask_rate must be <= 0.5")
+    c1 = torch.floor(view1_origin_coord.float().div(mask_grid_size))
+    c2 = torch.floor(view2_origin_coord.float().div(mask_grid_size))
+    cluster, patch_num = msc_patch_rank(c1, view1_offset, c2, view2_offset)
+    patch_num = int(patch_num.item())
+    perm = (torch.randperm if rand_perm is None else rand_perm)(patch_num)
+    k = int(patch_num * mask_rate)
+    patch_mask = torch.zeros(patch_num, dtype=torch.int32)
+    patch_mask[perm[0:k]] = 1
+    patch_mask[perm[k:k * 2]] = 2
+    return msc_patch_masks(cluster, patch_mask.to(cluster.device), c1.shape[0])
+
+
+def _msc_nce_args(feat1, feat2, match_index):
+    require_cuda(feat1, feat2, match_index)
+    if feat1.dtype != torch.float32 or feat2.dtype != torch.float32 or feat1.dim() != 2 or feat2.dim() != 2 or feat1.shape[1] != feat2.shape[1]:
+        raise PtcoreError("msc_nce: feat1 / feat2 must be fp32 [N, C] with equal C")
+    c = feat1.shape[1]
+    if c % 4 or not 4 <= c <= 256:
+        raise PtcoreError(f"msc_nce: C={c} is not a multiple of 4 in [4, 256]")
+    mi = match_index.to(torch.int64).contiguous()
+    if mi.dim() != 2 or mi.shape[1] != 2 or mi.shape[0] < 1:
+        raise PtcoreError("msc_nce: match_index must be [P, 2] with P >= 1")
+    return feat1.contiguous(), feat2.contiguous(), mi, c
+
+
+def msc_nce_fwd(feat1, feat2, match_index, nce_t: float):
+    """-> (out [3] fp32 = (nce loss, pos_sim, neg_sim) of :179-193, state for msc_nce_bwd); the P x P similarity matrix is never stored"""
+    f1, f2, mi, c = _msc_nce_args(feat1, feat2, match_index)
+    p, dev = mi.shape[0], f1.device
+    an = torch.empty((p, c), dtype=torch.float32, device=dev)
+    bn = torch.empty((p, c), dtype=torch.float32, device=dev)
+    vec = torch.empty((3, p), dtype=torch.float32, device=dev)        # |a|, |b|, lse
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    nbytes = lib().ptc_msc_nce_workspace_bytes(p, c)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_msc_nce_fwd(ptr(f1), f1.shape[0], ptr(f2), f2.shape[0], ptr(mi), p, c, float(nce_t), ptr(an), ptr(bn), ptr(vec[0]),
+                                ptr(vec[1]), ptr(vec[2]), ptr(out), ptr(ws), nbytes, stream_ptr()), "ptc_msc_nce_fwd")
+    return out, (an, bn, vec, mi)
+
+
+def msc_nce_bwd(state, n1: int, n2: int, nce_t: float, dloss: torch.Tensor):
+    """(dfeat1 [n1, C], dfeat2 [n2, C]) fp32 from the forward's state and d loss (a device scalar: no host read)"""
+    an, bn, vec, mi = state
+    p, c = an.shape
+    dev = an.device
+    d1 = torch.zeros((int(n1), c), dtype=torch.float32, device=dev)
+    d2 = torch.zeros((int(n2), c), dtype=torch.float32, device=dev)
+    g = dloss.to(torch.float32).reshape(1).contiguous()
+    nbytes = lib().ptc_msc_nce_workspace_bytes(p, c)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_msc_nce_bwd(ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(mi), p, c, int(n1), int(n2), float(nce_t),
+                                ptr(g), ptr(d1), ptr(d2), ptr(ws), nbytes, stream_ptr()), "ptc_msc_nce_bwd")
+    return d1, d2

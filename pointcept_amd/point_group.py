@@ -14,8 +14,6 @@ bias_head.{0,1,3}.*, seg_head.*) and return dicts.  Registered only when named: 
 """
 from __future__ import annotations
 
-import importlib
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -24,24 +22,8 @@ from . import config as _config
 from . import functional as PF
 from . import nn as PNN
 from . import ops
+from .compat import build_backbone  # noqa: F401  (its first home; kept importable from here)
 from .structure import Point, batch2offset, offset2batch
-
-
-def build_backbone(cfg):
-    """an engine backbone from a config dict (its `type` one of compat.MODEL_CLASSES / OPT_IN_MODEL_CLASSES), else the
-    reference's registry (inside a Pointcept checkout); a module is taken as is"""
-    if isinstance(cfg, nn.Module):
-        return cfg
-    from .compat import MODEL_CLASSES, OPT_IN_MODEL_CLASSES
-
-    kw = dict(cfg)
-    name = kw.pop("type")
-    if name in MODEL_CLASSES or name in OPT_IN_MODEL_CLASSES:
-        mod, cls = MODEL_CLASSES.get(name) or OPT_IN_MODEL_CLASSES[name]
-        return getattr(importlib.import_module(f"{__package__}.{mod}"), cls)(**kw)
-    from pointcept.models.builder import build_model
-
-    return build_model(cfg)
 
 
 class _Criteria:

@@ -205,3 +205,45 @@ def indoor_instance_batch(seeds, sizes):
     for sc in scenes:
         sc.pop("bbox")
     return collate(scenes)
+
+
+def contrastive_views(seed: int, point_max: int = 102400, grid: float = 0.02, shift=(-1.3, 0.4, -0.2), jitter: float = 0.004):
+    """Two views of one indoor scene as ContrastiveViewsGenerator + the MSC config's pipelines leave them
+    (configs/scannet/pretrain-msc-v1m1-0-spunet-base.py): each an independent sphere crop of about `point_max` points (the crops
+    overlap in part), rotated about z and jittered, voxelised at `grid` (one point per voxel).  Per view: origin_coord (the scene's
+    coordinate before the augmentation, shifted by `shift` so that some are negative: points shared by both crops keep equal origin
+    coordinates), coord, grid_coord, color, normal, feat = color | normal, under view1_* / view2_* keys."""
+    rng = np.random.default_rng(seed)
+    s = indoor_scene(seed, int(point_max * 1.6), grid)
+    origin = (s["coord"] + np.asarray(shift, np.float32)).astype(np.float32)
+    n = origin.shape[0]
+    take = min(point_max, n)
+    c1 = origin[rng.integers(n)]
+    near = np.argsort(((origin - c1) ** 2).sum(1), kind="stable")
+    c2 = origin[near[int(rng.integers(take // 8, max(take // 2, take // 8 + 1)))]]
+    out = {}
+    for v, c in (("view1", c1), ("view2", c2)):
+        d2 = ((origin - c) ** 2).sum(1)
+        keep = np.argpartition(d2, take - 1)[:take] if take < n else np.arange(n)
+        a = rng.uniform(0, 2 * np.pi)
+        rot = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+        p = (origin[keep] - c) @ rot.T + rng.normal(0, jitter, (keep.shape[0], 3))
+        gc = np.floor(p / grid).astype(np.int64)
+        gc -= gc.min(0)
+        _, first = np.unique((gc[:, 0] * 8192 + gc[:, 1]) * 8192 + gc[:, 2], return_index=True)
+        first = first[rng.permutation(first.shape[0])]
+        keep, p, gc = keep[first], p[first], gc[first]
+        colour = s["feat"][keep, :3]
+        normal = (s["feat"][keep, 3:] @ rot.T).astype(np.float32)
+        out.update({f"{v}_origin_coord": origin[keep], f"{v}_coord": p.astype(np.float32), f"{v}_grid_coord": gc,
+                    f"{v}_color": colour, f"{v}_normal": normal, f"{v}_feat": np.concatenate([colour, normal], 1)})
+    return out
+
+
+def contrastive_views_batch(seeds, sizes, **kw):
+    """collated contrastive_views scenes with view1_offset / view2_offset (point_collate_fn on the view keys)"""
+    scenes = [contrastive_views(s, n, **kw) for s, n in zip(seeds, sizes)]
+    out = {k: np.concatenate([sc[k] for sc in scenes]) for k in scenes[0]}
+    for v in ("view1", "view2"):
+        out[f"{v}_offset"] = np.cumsum([sc[f"{v}_coord"].shape[0] for sc in scenes]).astype(np.int64)
+    return out
