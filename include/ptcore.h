@@ -845,6 +845,39 @@ int ptc_msc_nce_bwd(const float* an, const float* bn, const float* na, const flo
                     int64_t p, int c, int64_t n1, int64_t n2, float nce_t, const float* dloss, float* dfeat1, float* dfeat2,
                     void* workspace, size_t workspace_bytes, ptc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Context-aware classifier (csrc/cac.hip; pointcept/models/context_aware_classifier/context_aware_classifier_v1m1_base.py).
+ * fp32; 2 <= k <= 256 classes, c a multiple of 16 in [16, 128] (ptc_cac_supported; PTC_EUNSUPPORTED otherwise), s <= 512 segments.
+ * offset [s] int64: the cumulative row ends of the segments (NULL with s = 1: all n rows).  No float atomics: bit-reproducible.
+ * ptc_cac_pool_fwd: proto [s,k,c] = sum_i w_ik x_i / (sum_i w_ik + eps), wsum [s,k] = sum_i w_ik, passed [s] = rows with weight.
+ *   logits [n,k] (soft): w_i = softmax(logits_i), times [max_k w_ik >= conf_thresh] when conf_thresh > 0;
+ *   target [n] (hard, s = 1): w_i = onehot(target_i), rows outside [0, k) carry none; count [k] = the class counts (exact).
+ *   Exactly one of logits / target is non-NULL.  A class without weight gives a zero row (the caller blends).
+ * ptc_cac_pool_bwd: dx [n,c] and, soft only and when dlogits != NULL, dlogits [n,k], from dproto [s,k,c]; the softmax is recomputed.
+ * ptc_cac_cos_fwd: out [n,k] = cos_temp normalize(x_i) . normalize(proto[s(i), k]), both with F.normalize's max(|.|, 1e-12).
+ * ptc_cac_cos_bwd: dx [n,c], dproto [s,k,c] from dout [n,k].
+ * ptc_cac_distill_fwd: get_distill_loss(pred, soft, target, smoothness, eps) -> loss [1]; stats [3,k] = per-class sums of
+ *   loss * entropy, of entropy, and row counts (kept for the backward).  ptc_cac_distill_bwd: dpred [n,k] = d loss / d pred * dloss[0].
+ * ------------------------------------------------------------------------------------------ */
+int ptc_cac_supported(int k, int c);
+size_t ptc_cac_pool_workspace_bytes(int64_t n, int s, int k, int c);
+int ptc_cac_pool_fwd(const float* x, const float* logits, const int64_t* target, const int64_t* offset, int64_t n, int s, int k, int c,
+                     float conf_thresh, float eps, float* proto, float* wsum, int64_t* count, int64_t* passed, void* workspace,
+                     size_t workspace_bytes, ptc_stream_t stream);
+int ptc_cac_pool_bwd(const float* x, const float* logits, const int64_t* target, const int64_t* offset, int64_t n, int s, int k, int c,
+                     float conf_thresh, float eps, const float* proto, const float* wsum, const float* dproto, float* dx, float* dlogits,
+                     ptc_stream_t stream);
+size_t ptc_cac_cos_workspace_bytes(int64_t n, int s, int k, int c);
+int ptc_cac_cos_fwd(const float* x, const float* proto, const int64_t* offset, int64_t n, int s, int k, int c, float cos_temp, float* out,
+                    void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+int ptc_cac_cos_bwd(const float* x, const float* proto, const int64_t* offset, int64_t n, int s, int k, int c, float cos_temp,
+                    const float* dout, float* dx, float* dproto, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+size_t ptc_cac_distill_workspace_bytes(int64_t n, int k);
+int ptc_cac_distill_fwd(const float* pred, const float* soft, const int64_t* target, int64_t n, int k, float smoothness, float eps,
+                        float* loss, float* stats, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+int ptc_cac_distill_bwd(const float* pred, const float* soft, const int64_t* target, int64_t n, int k, float smoothness, float eps,
+                        const float* stats, const float* dloss, float* dpred, ptc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,17 @@ _SIGNATURES = {
                                 c_size, c_ptr]),
     "ptc_msc_nce_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_i64, c_i64, c_f32, c_ptr, c_ptr, c_ptr, c_ptr,
                                 c_size, c_ptr]),
+    "ptc_cac_supported": (c_int, [c_int, c_int]),
+    "ptc_cac_pool_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
+    "ptc_cac_pool_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size,
+                                 c_ptr]),
+    "ptc_cac_pool_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "ptc_cac_cos_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
+    "ptc_cac_cos_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_cac_cos_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_cac_distill_workspace_bytes": (c_size, [c_i64, c_int]),
+    "ptc_cac_distill_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_cac_distill_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "ptc_lovasz_softmax_workspace_bytes": (c_size, [c_i64, c_int]),
     "ptc_lovasz_softmax": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
 }

@@ -53,6 +53,7 @@ HIP_SOURCES = [
     "cluster_agg.hip",
     "pg_cluster.hip",
     "msc.hip",
+    "cac.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

@@ -1404,3 +1404,184 @@ def msc_select_torch(count: torch.Tensor, cand: torch.Tensor, r: torch.Tensor) -
     _, cnt = index[:, 0].unique(return_counts=True)
     select = torch.cumsum(cnt, dim=0) - r.to(cnt.device) % cnt - 1
     return index[select]
+
+
+# ------------------------------------------------------------------------------------------------
+# Context-aware classifier (context_aware_classifier_v1m1_base.py): prototype pooling, cosine classifier, distillation loss.
+# Each kernel Function has a *_torch twin: the reference's own expression, loops included, device-neutral -- the A/B baseline
+# (PTC_CAC=0), the CPU path, and what the wrapper takes for shapes the kernels refuse.
+# ------------------------------------------------------------------------------------------------
+def _cac_bounds(offset, n):
+    if offset is None:
+        return [(0, n)]
+    ends = [int(e) for e in offset.tolist()]
+    return list(zip([0] + ends[:-1], ends))
+
+
+class _CACPoolSoft(Function):
+    @staticmethod
+    def forward(ctx, x, logits, offset, conf_thresh, eps):
+        x, logits = x.contiguous(), logits.contiguous()
+        proto, wsum, _, passed = ops.cac_pool_fwd(x, logits=logits, offset=offset, conf_thresh=conf_thresh, eps=eps)
+        ctx.save_for_backward(x, logits, proto, wsum)
+        ctx.args = (offset, float(conf_thresh), float(eps))
+        ctx.mark_non_differentiable(wsum, passed)
+        return proto, wsum, passed
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dproto, _dw, _dp):
+        x, logits, proto, wsum = ctx.saved_tensors
+        offset, thresh, eps = ctx.args
+        dx, dl = ops.cac_pool_bwd(x, logits, None, offset, thresh, eps, proto, wsum, dproto, ctx.needs_input_grad[1])
+        return (dx if ctx.needs_input_grad[0] else None), dl, None, None, None
+
+
+def cac_pool_soft(x, logits, offset=None, conf_thresh: float = 0.0, eps: float = 1e-7):
+    """(proto [S, K, C], wsum [S, K], passed [S]) of post_refine_proto_batch (:111-117, :134-142) for all scenes at once:
+    proto[s] = (p / (p.sum(-1) + eps)) @ x over the rows of scene s, p = softmax(logits) times the confidence gate.  Differentiable
+    in x and logits.  fp32 kernels: 16-bit inputs are cast up."""
+    with torch.autocast(device_type=x.device.type, enabled=False):
+        return _CACPoolSoft.apply(x.float(), logits.float(), offset, float(conf_thresh), float(eps))
+
+
+def cac_pool_soft_torch(x, logits, offset=None, conf_thresh: float = 0.0, eps: float = 1e-7):
+    protos, sums, passed = [], [], []
+    for start, end in _cac_bounds(offset, x.shape[0]):
+        pred = F.softmax(logits[start:end], 1).permute(1, 0)
+        if conf_thresh > 0:
+            max_pred = (pred.max(0)[0] >= conf_thresh).to(pred.dtype).unsqueeze(0)
+            passed.append(max_pred.sum())
+            pred = pred * max_pred
+        else:
+            passed.append(torch.as_tensor(float(end - start), device=x.device))
+        sums.append(pred.sum(-1))
+        protos.append((pred / (pred.sum(-1).unsqueeze(-1) + eps)) @ x[start:end])
+    return torch.stack(protos), torch.stack(sums).detach(), torch.stack(passed).long()
+
+
+class _CACPoolHard(Function):
+    @staticmethod
+    def forward(ctx, x, target, num_classes, eps):
+        proto, wsum, count, _ = ops.cac_pool_fwd(x, target=target, num_classes=num_classes, eps=eps)
+        ctx.save_for_backward(x, target.to(torch.int64).contiguous(), proto, wsum)
+        ctx.eps = float(eps)
+        ctx.mark_non_differentiable(count)
+        return proto[0], count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dproto, _dc):
+        x, target, proto, wsum = ctx.saved_tensors
+        dx, _ = ops.cac_pool_bwd(x, None, target, None, 0.0, ctx.eps, proto, wsum, dproto.unsqueeze(0), False)
+        return dx, None, None, None
+
+
+def cac_pool_hard(x, target, base, eps: float = 1e-4):
+    """(new_proto [K, C], count [K]) of get_adaptive_perspective's class loop (:78-90): the rows of `base` whose class occurs in
+    `target` replaced by sum_{target == k} x / (count_k + eps); rows with target -1 take no part; absent classes keep their row."""
+    with torch.autocast(device_type=x.device.type, enabled=False):
+        proto, count = _CACPoolHard.apply(x.float(), target, base.shape[0], float(eps))
+        return torch.where((count > 0).unsqueeze(-1), proto, base.float()), count
+
+
+def cac_pool_hard_torch(x, target, base, eps: float = 1e-4):
+    new_proto = base
+    unique_y = [y for y in target.unique() if int(y) != -1]
+    t = target.unsqueeze(-1)
+    for tmp_y in unique_y:
+        tmp_mask = (t == tmp_y).to(x.dtype)
+        tmp_proto = (x * tmp_mask).sum(0) / (tmp_mask.sum(0) + eps)
+        onehot_vec = torch.zeros(new_proto.shape[0], 1, dtype=x.dtype, device=x.device)
+        onehot_vec[tmp_y.long()] = 1
+        new_proto = new_proto * (1 - onehot_vec) + tmp_proto.unsqueeze(0) * onehot_vec
+    count = torch.bincount(target[target >= 0], minlength=base.shape[0])
+    return new_proto, count
+
+
+class _CACCos(Function):
+    @staticmethod
+    def forward(ctx, x, proto, offset, cos_temp):
+        ctx.save_for_backward(x, proto)
+        ctx.args = (offset, float(cos_temp))
+        return ops.cac_cos_fwd(x, proto, offset, cos_temp)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        x, proto = ctx.saved_tensors
+        offset, cos_temp = ctx.args
+        dx, dp = ops.cac_cos_bwd(x, proto, offset, cos_temp, dout)
+        return dx, dp, None, None
+
+
+def cac_cos_logits(x, proto, offset=None, cos_temp: float = 1.0):
+    """get_pred (:66-71) times cos_temp for all scenes at once: out[i] = cos_temp * normalize(x_i) @ normalize(proto[s(i)]).T with
+    proto [S, K, C] (or [K, C]: one set for every row).  Differentiable in x and proto.  fp32 kernels: 16-bit inputs are cast up."""
+    with torch.autocast(device_type=x.device.type, enabled=False):
+        p = proto.float()
+        return _CACCos.apply(x.float(), p.unsqueeze(0) if p.dim() == 2 else p, offset if proto.dim() == 3 else None, float(cos_temp))
+
+
+def cac_cos_logits_torch(x, proto, offset=None, cos_temp: float = 1.0):
+    if proto.dim() == 2:
+        return F.normalize(x, 2, 1) @ F.normalize(proto, 2, 1).permute(1, 0) * cos_temp
+    out = [F.normalize(x[start:end], 2, 1) @ F.normalize(proto[i], 2, 1).permute(1, 0)
+           for i, (start, end) in enumerate(_cac_bounds(offset, x.shape[0]))]
+    return torch.cat(out, 0) * cos_temp
+
+
+class _CACDistill(Function):
+    @staticmethod
+    def forward(ctx, pred, soft, target, smoothness, eps):
+        loss, stats, state = ops.cac_distill_fwd(pred, soft, target, smoothness, eps)
+        ctx.save_for_backward(stats, *state)
+        ctx.args = (float(smoothness), float(eps))
+        return loss[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss):
+        stats, pred, soft, tg = ctx.saved_tensors
+        return ops.cac_distill_bwd((pred, soft, tg), ctx.args[0], ctx.args[1], stats, dloss), None, None, None, None
+
+
+def cac_distill(pred, soft, target, smoothness: float = 0.5, eps: float = 0):
+    """get_distill_loss (:152-199): class-wise entropy-weighted distillation of softmax(soft) (detached) into pred; a scalar,
+    differentiable in pred.  fp32 kernels: 16-bit inputs are cast up."""
+    with torch.autocast(device_type=pred.device.type, enabled=False):
+        return _CACDistill.apply(pred.float(), soft.detach().float(), target, float(smoothness), float(eps))
+
+
+def cac_distill_torch(pred, soft, target, smoothness: float = 0.5, eps: float = 0):
+    n, c = soft.shape[:]
+    soft = soft.detach()
+    target = target.unsqueeze(-1)
+    onehot = target.view(-1, 1)
+    ignore_mask = (onehot == -1).to(soft.dtype)
+    sm_soft = F.softmax(soft / 1, 1)
+    onehot = onehot * (1 - ignore_mask)
+    onehot = torch.zeros(n, c, dtype=soft.dtype, device=soft.device).scatter_(1, onehot.long(), 1)
+    smoothed_label = smoothness * sm_soft + (1 - smoothness) * onehot
+    if eps > 0:
+        smoothed_label = smoothed_label * (1 - eps) + (1 - smoothed_label) * eps / (smoothed_label.shape[1] - 1)
+    loss = torch.mul(-1 * F.log_softmax(pred, dim=1), smoothed_label)
+    loss = loss.sum(1)
+    sm_soft = F.softmax(soft / 1, 1)
+    entropy_mask = -1 * (sm_soft * torch.log(sm_soft + 1e-4)).sum(1)
+    target = target.squeeze(-1)
+    unique_classes = [y for y in target.unique() if int(y) != -1]
+    valid_mask = (target != -1).to(soft.dtype)
+    entropy_mask = entropy_mask * valid_mask
+    loss_list = []
+    weight_list = []
+    for tmp_y in unique_classes:
+        tmp_mask = (target == tmp_y).to(soft.dtype).squeeze()
+        tmp_entropy_mask = entropy_mask * tmp_mask
+        class_weight = 1
+        tmp_loss = (loss * tmp_entropy_mask).sum() / (tmp_entropy_mask.sum() + 1e-4)
+        loss_list.append(class_weight * tmp_loss)
+        weight_list.append(class_weight)
+    if len(weight_list) > 0:
+        return sum(loss_list) / (sum(weight_list) + 1e-4)
+    return torch.zeros(1, dtype=pred.dtype, device=pred.device).mean()

@@ -1761,3 +1761,126 @@ def msc_nce_bwd(state, n1: int, n2: int, nce_t: float, dloss: torch.Tensor):
     check(lib().ptc_msc_nce_bwd(ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(mi), p, c, int(n1), int(n2), float(nce_t),
                                 ptr(g), ptr(d1), ptr(d2), ptr(ws), nbytes, stream_ptr()), "ptc_msc_nce_bwd")
     return d1, d2
+
+
+# ------------------------------------------------------------------------------------------------
+# context-aware classifier (csrc/cac.hip): prototype pooling, segmented cosine classifier, distillation loss
+# ------------------------------------------------------------------------------------------------
+def cac_supported(k: int, c: int) -> bool:
+    return bool(lib().ptc_cac_supported(int(k), int(c)))
+
+
+def _cac_rows(x: torch.Tensor, what: str) -> torch.Tensor:
+    require_cuda(x)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise PtcoreError(f"{what}: needs fp32 [N, C] rows, got {x.dtype} {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def _cac_offset(offset, device):
+    if offset is None:
+        return None, 1
+    o = offset.to(device=device, dtype=torch.int64).contiguous()
+    return o, int(o.numel())
+
+
+def cac_pool_fwd(x, logits=None, target=None, offset=None, num_classes=None, conf_thresh: float = 0.0, eps: float = 1e-7):
+    """-> (proto [S, K, C], wsum [S, K], count [K] int64 | None, passed [S] int64).  logits [N, K]: w_i = softmax(logits_i) times the
+    confidence gate, rows segmented by `offset`; target [N] (needs num_classes): w_i = onehot(target_i), one segment, count = the
+    class counts.  proto = sum_i w_ik x_i / (sum_i w_ik + eps); the weights are never written to memory."""
+    x = _cac_rows(x, "cac_pool_fwd")
+    n, c = x.shape
+    hard = target is not None
+    if hard == (logits is not None):
+        raise PtcoreError("cac_pool_fwd: exactly one of logits / target")
+    if hard:
+        require_cuda(target)
+        target = target.to(torch.int64).contiguous()
+        k, off, s = int(num_classes), None, 1
+    else:
+        logits = _cac_rows(logits, "cac_pool_fwd")
+        k = logits.shape[1]
+        off, s = _cac_offset(offset, x.device)
+    dev = x.device
+    proto = torch.empty((s, k, c), dtype=torch.float32, device=dev)
+    wsum = torch.empty((s, k), dtype=torch.float32, device=dev)
+    count = torch.empty(k, dtype=torch.int64, device=dev) if hard else None
+    passed = torch.empty(s, dtype=torch.int64, device=dev)
+    nbytes = lib().ptc_cac_pool_workspace_bytes(n, s, k, c)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_cac_pool_fwd(ptr(x), ptr(logits), ptr(target), ptr(off), n, s, k, c, float(conf_thresh), float(eps), ptr(proto), ptr(wsum),
+                                 ptr(count), ptr(passed), ptr(ws), nbytes, stream_ptr()), "ptc_cac_pool_fwd")
+    return proto, wsum, count, passed
+
+
+def cac_pool_bwd(x, logits, target, offset, conf_thresh: float, eps: float, proto, wsum, dproto, need_dlogits: bool):
+    """(dx [N, C], dlogits [N, K] | None) of cac_pool_fwd; the softmax rows are recomputed"""
+    x = _cac_rows(x, "cac_pool_bwd")
+    n, c = x.shape
+    s, k = wsum.shape
+    off, _ = _cac_offset(offset, x.device)
+    dx = torch.empty_like(x)
+    if logits is not None:
+        logits = _cac_rows(logits, "cac_pool_bwd")
+    dl = torch.empty_like(logits) if (need_dlogits and logits is not None) else None
+    dp = dproto.to(torch.float32).contiguous()          # kept in a name: the copy must outlive the call
+    check(lib().ptc_cac_pool_bwd(ptr(x), ptr(logits), ptr(target), ptr(off), n, s, k, c, float(conf_thresh), float(eps), ptr(proto), ptr(wsum),
+                                 ptr(dp), ptr(dx), ptr(dl), stream_ptr()), "ptc_cac_pool_bwd")
+    return dx, dl
+
+
+def cac_cos_fwd(x, proto, offset, cos_temp: float):
+    """out [N, K] = cos_temp * normalize(x_i) . normalize(proto[s(i), k]); proto [S, K, C]"""
+    x, p = _cac_rows(x, "cac_cos_fwd"), proto.contiguous()
+    n, c = x.shape
+    s, k = p.shape[0], p.shape[1]
+    off, so = _cac_offset(offset, x.device)
+    if p.dim() != 3 or p.shape[2] != c or p.dtype != torch.float32 or so != s:
+        raise PtcoreError(f"cac_cos_fwd: prototypes {tuple(p.shape)} {p.dtype} for rows {tuple(x.shape)} in {so} segment(s)")
+    out = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    nbytes = lib().ptc_cac_cos_workspace_bytes(n, s, k, c)
+    ws = _ws(nbytes, x.device)
+    check(lib().ptc_cac_cos_fwd(ptr(x), ptr(p), ptr(off), n, s, k, c, float(cos_temp), ptr(out), ptr(ws), nbytes, stream_ptr()), "ptc_cac_cos_fwd")
+    return out
+
+
+def cac_cos_bwd(x, proto, offset, cos_temp: float, dout):
+    """(dx [N, C], dproto [S, K, C]) of cac_cos_fwd; dproto is reduced per segment in a fixed order"""
+    x, p = _cac_rows(x, "cac_cos_bwd"), proto.contiguous()
+    n, c = x.shape
+    s, k = p.shape[0], p.shape[1]
+    off, _ = _cac_offset(offset, x.device)
+    dx, dp = torch.empty_like(x), torch.empty_like(p)
+    nbytes = lib().ptc_cac_cos_workspace_bytes(n, s, k, c)
+    ws = _ws(nbytes, x.device)
+    do = dout.to(torch.float32).contiguous()            # kept in a name: the copy must outlive the call
+    check(lib().ptc_cac_cos_bwd(ptr(x), ptr(p), ptr(off), n, s, k, c, float(cos_temp), ptr(do), ptr(dx), ptr(dp), ptr(ws), nbytes,
+                                stream_ptr()), "ptc_cac_cos_bwd")
+    return dx, dp
+
+
+def cac_distill_fwd(pred, soft, target, smoothness: float, eps: float):
+    """-> (loss [1], stats [3, K]) of get_distill_loss (:152-199); stats = per-class sums of loss * entropy, entropy, row counts"""
+    pred, soft = _cac_rows(pred, "cac_distill_fwd"), _cac_rows(soft, "cac_distill_fwd")
+    require_cuda(target)
+    n, k = pred.shape
+    if soft.shape != pred.shape or target.shape != (n,):
+        raise PtcoreError(f"cac_distill_fwd: pred {tuple(pred.shape)}, soft {tuple(soft.shape)}, target {tuple(target.shape)}")
+    tg = target.to(torch.int64).contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    stats = torch.empty((3, k), dtype=torch.float32, device=pred.device)
+    nbytes = lib().ptc_cac_distill_workspace_bytes(n, k)
+    ws = _ws(nbytes, pred.device)
+    check(lib().ptc_cac_distill_fwd(ptr(pred), ptr(soft), ptr(tg), n, k, float(smoothness), float(eps), ptr(loss), ptr(stats), ptr(ws), nbytes,
+                                    stream_ptr()), "ptc_cac_distill_fwd")
+    return loss, stats, (pred, soft, tg)
+
+
+def cac_distill_bwd(state, smoothness: float, eps: float, stats, dloss):
+    pred, soft, tg = state
+    n, k = pred.shape
+    dpred = torch.empty_like(pred)
+    g = dloss.to(torch.float32).reshape(1).contiguous()
+    check(lib().ptc_cac_distill_bwd(ptr(pred), ptr(soft), ptr(tg), n, k, float(smoothness), float(eps), ptr(stats), ptr(g), ptr(dpred),
+                                    stream_ptr()), "ptc_cac_distill_bwd")
+    return dpred
