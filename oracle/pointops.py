@@ -1,5 +1,6 @@
-"""TEST INFRASTRUCTURE (oracle).  numpy restatements of two pointops kernels that exist only as CUDA in the reference
-(libs/pointops/src/knn_query/knn_query_cuda_kernel.cu:60-108, src/sampling/sampling_cuda_kernel.cu:15-122) --
+"""TEST INFRASTRUCTURE (oracle).  numpy restatements of the pointops query / sampling kernels that exist only as CUDA in the
+reference (libs/pointops/src/knn_query/knn_query_cuda_kernel.cu:60-108, src/sampling/sampling_cuda_kernel.cu:15-122, the two ball
+queries), and of the python wrapper built on the k-NN (functions/interpolation.py, float64) --
 "parity unpinned": they cannot be executed here; semantics follow the kernels' loops, with the tie order the reference
 leaves implementation-defined fixed to "lower index first".  fp32 arithmetic, ((dx*dx + dy*dy) + dz*dz), like the kernels."""
 from __future__ import annotations
@@ -43,6 +44,27 @@ def farthest_point_sampling(xyz, offset, new_offset):
                 out[j] = old
         s0, q0 = s1, q1
     return out
+
+
+def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3, grad_out=None):
+    """libs/pointops/functions/interpolation.py:8-24 in float64 over this file's knn_query (fp32 distances, as the wrapper
+    receives them): recip = 1 / (dist + 1e-8), weight = recip / recip.sum(1), out = sum_i weight_i feat[idx_i].  A -1 slot
+    (scene with fewer than k points: dist 1e5) keeps its ~1e-5 share of the normaliser and contributes zero -- the port's
+    grouping convention; the reference indexes feat[-1] there.  -> out [m, c], or (out, d_feat [n, c]) for a given
+    grad_out [m, c]: the transposed weighted scatter (interpolation_backward_cuda)."""
+    idx, dist = knn_query(k, xyz, offset, new_xyz, new_offset)
+    recip = 1.0 / (dist.astype(np.float64) + 1e-8)
+    weight = recip / recip.sum(1, keepdims=True)
+    feat = np.asarray(feat, dtype=np.float64)
+    live = idx >= 0
+    safe = np.where(live, idx, 0)
+    w = np.where(live, weight, 0.0)
+    out = (w[:, :, None] * feat[safe]).sum(1)
+    if grad_out is None:
+        return out
+    d_feat = np.zeros_like(feat)
+    np.add.at(d_feat, safe.reshape(-1), (w[:, :, None] * np.asarray(grad_out, dtype=np.float64)[:, None, :]).reshape(-1, feat.shape[1]))
+    return out, d_feat
 
 
 def ball_query(nsample, max_radius, min_radius, xyz, offset, new_xyz, new_offset, order=None):

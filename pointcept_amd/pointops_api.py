@@ -109,7 +109,14 @@ class _EdgeInterpolate(torch.autograd.Function):
 
 
 def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
-    """libs/pointops/functions/interpolation.py:8-27: inverse-distance weighting over the k nearest source points (fp32 result)."""
+    """libs/pointops/functions/interpolation.py:8-27: inverse-distance weighting over the k nearest source points of the target's
+    scene (fp32 result): weight_i = recip_i / sum_j recip_j with recip = 1 / (dist + 1e-8), out = sum_i weight_i feat[idx_i];
+    the gradient of feat is the transposed weighted scatter, as a fixed-order segmented sum.
+    One difference from the reference, in scenes with FEWER THAN k source points: their empty slots carry idx -1 / dist 1e5, so
+    a weight of about 1e-5 relative to a neighbour at unit distance, and they keep that share of the normaliser on both sides.
+    The reference then indexes feat[-1] -- the LAST row of the whole batch, a point of another scene -- and adds it with that
+    weight; here a -1 slot gathers zero (the grouping convention), in the forward and in the gradient.  The results differ by
+    about 1e-5 |feat| per empty slot, and the weights of such a row sum to slightly less than 1."""
     idx, dist = knn_query(k, xyz, offset, new_xyz, new_offset)
     recip = 1.0 / (dist + 1e-8)
     weight = recip / recip.sum(dim=1, keepdim=True)

@@ -149,3 +149,67 @@ def test_pointops2_oracle_against_the_kernels_index_arithmetic():
     off = orc.offsets_of(i0, N)
     assert off.numel() == N + 1 and int(off[-1]) == M and all(int(off[n]) <= int(off[n + 1]) for n in range(N))
 
+
+
+def test_pointops_interpolation_oracle_matches_the_reference_expression():
+    """oracle.pointops.interpolation (what tests/test_gpu_pointops_limits.py holds the kernels to) against the reference's
+    own expression (libs/pointops/functions/interpolation.py:8-24) evaluated by torch in float64 with autograd, on scenes
+    with at least k points (no -1 slots, where the two agree by definition); coinciding points give zero distances."""
+    from oracle import pointops as opo
+
+    rng = np.random.default_rng(7)
+    sizes, qsizes, c = [40, 9, 17], [25, 6, 30], 5
+    xyz = rng.random((sum(sizes), 3)).astype(np.float32)
+    new_xyz = rng.random((sum(qsizes), 3)).astype(np.float32)
+    new_xyz[:10] = xyz[:10]
+    new_xyz[-4:] = xyz[-4:]
+    off, noff = np.cumsum(sizes), np.cumsum(qsizes)
+    feat = rng.standard_normal((sum(sizes), c))
+    probe = rng.standard_normal((sum(qsizes), c))
+    for k in (1, 3, 8):
+        idx, dist = opo.knn_query(k, xyz, off, new_xyz, noff)
+        assert (idx >= 0).all()
+        f = torch.from_numpy(feat).requires_grad_(True)
+        d = torch.from_numpy(dist).double()
+        dist_recip = 1.0 / (d + 1e-8)
+        norm = torch.sum(dist_recip, dim=1, keepdim=True)
+        weight = dist_recip / norm
+        new_feat = torch.zeros((new_xyz.shape[0], c), dtype=torch.float64)
+        for i in range(k):
+            new_feat = new_feat + f[torch.from_numpy(idx[:, i]).long(), :] * weight[:, i].unsqueeze(-1)
+        (new_feat * torch.from_numpy(probe)).sum().backward()
+        out, d_feat = opo.interpolation(xyz, new_xyz, feat, off, noff, k, grad_out=probe)
+        assert np.allclose(out, new_feat.detach().numpy(), rtol=0, atol=1e-12)
+        assert np.allclose(d_feat, f.grad.numpy(), rtol=0, atol=1e-12)
+        assert np.array_equal(opo.interpolation(xyz, new_xyz, feat, off, noff, k), out)
+    # fewer points than k: the -1 slots keep their share of the normaliser and gather zero
+    out = opo.interpolation(xyz[:2], new_xyz[:3], np.ones((2, 1)), np.array([2]), np.array([3]), 4)
+    _, dist = opo.knn_query(4, xyz[:2], np.array([2]), new_xyz[:3], np.array([3]))
+    recip = 1.0 / (dist.astype(np.float64) + 1e-8)
+    assert np.allclose(out[:, 0], recip[:, :2].sum(1) / recip.sum(1), rtol=0, atol=1e-15) and (out < 1.0).all()
+
+
+def test_pointops_ball_query_oracle_candidate_cap_by_brute_force():
+    """oracle.pointops.ball_query on a scene with more than 2048 in-range points against a brute force that restates the
+    candidate bound of ball_query_cuda_kernel.cu on its own: in-range indices, the first 2048 of them, a stable sort by distance."""
+    from oracle import pointops as opo
+
+    rng = np.random.default_rng(8)
+    n, rmax = 2600, 0.75
+    xyz = rng.random((n, 3)).astype(np.float32)
+    xyz[[2100, 2599, 5]] = np.float32(0.5) + np.float32(0.05) * xyz[[2100, 2599, 5]]          # near the centre: most of the cube in range
+    new_xyz = np.concatenate([xyz[[2100, 2599, 5]], (0.4 + 0.2 * rng.random((3, 3))).astype(np.float32)])
+    off, noff = np.array([n]), np.array([len(new_xyz)])
+    full_i, full_d = opo.ball_query(2048, rmax, 0.0, xyz, off, new_xyz, noff)
+    sub_i, sub_d = opo.ball_query(100, rmax, 0.0, xyz, off, new_xyz, noff)
+    ranks = (np.float32(2048) / np.float32(100) * np.arange(100, dtype=np.float32)).astype(np.int32)
+    for q in range(len(new_xyz)):
+        diff = xyz - new_xyz[q]
+        d2 = (diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1]) + diff[:, 2] * diff[:, 2]
+        cand = np.nonzero(d2 < np.float32(rmax) * np.float32(rmax))[0]
+        assert 2048 < len(cand) < n                                     # over the cap, and the radius does exclude something
+        cand = cand[:2048]
+        cand = cand[np.argsort(d2[cand], kind="stable")]
+        assert np.array_equal(full_i[q], cand) and np.array_equal(full_d[q], np.sqrt(d2[cand]))
+        assert np.array_equal(sub_i[q], cand[ranks]) and np.array_equal(sub_d[q], np.sqrt(d2[cand[ranks]]))
+    assert 2100 not in full_i[0] and 2599 not in full_i[1] and full_i[2, 0] == 5    # a copied point past the cap is not found
