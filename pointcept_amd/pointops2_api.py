@@ -32,6 +32,15 @@ def _i32(t):
     return t if t.dtype == torch.int32 else t.to(torch.int32)
 
 
+def _offsets(index0_offsets, n_rows: int, what: str) -> torch.Tensor:
+    """the CSR offsets as contiguous int32, refused here unless there is one segment per query row: every kernel of the offsets
+    forms, forward included, is sized by the rows and reads offsets[n] and offsets[n + 1] of each"""
+    off = _i32(index0_offsets).contiguous()
+    if off.dim() != 1 or off.numel() != n_rows + 1:
+        raise ops.PtcoreError(f"{what}: offsets must have {n_rows + 1} entries (one segment per query row), got {tuple(off.shape)}")
+    return off
+
+
 def _index_from_offsets(offsets: torch.Tensor, m: int) -> torch.Tensor:
     """query index of every pair from the CSR offsets [Nq+1] (the inverse of what the models do with `index_0_offsets`)"""
     counts = (offsets[1:] - offsets[:-1]).long()
@@ -161,7 +170,7 @@ def attention_step1(q, k, index0, index1):
 
 def attention_step1_v2(q, k, index1, index0_offsets, n_max):
     q, k = _prep(q, k)
-    off, i1 = _i32(index0_offsets).contiguous(), _i32(index1).contiguous()
+    off, i1 = _offsets(index0_offsets, q.shape[0], "attention_step1_v2"), _i32(index1).contiguous()
     return _PairDot.apply(q, k, None, None, _index_from_offsets(off, i1.numel()), off, i1, None, True)
 
 
@@ -178,7 +187,7 @@ def dot_prod_with_idx_v2(q, index_q, k, index_k, table_q, table_k, rel_idx):
 
 def dot_prod_with_idx_v3(q, index_q_offsets, n_max, k, index_k, table_q, table_k, rel_idx):
     q, k, table_q, table_k = _prep(q, k, table_q, table_k)
-    off, i1 = _i32(index_q_offsets).contiguous(), _i32(index_k).contiguous()
+    off, i1 = _offsets(index_q_offsets, q.shape[0], "dot_prod_with_idx_v3"), _i32(index_k).contiguous()
     return _PairDot.apply(q, k, table_q, table_k, _index_from_offsets(off, i1.numel()), off, i1, _i32(rel_idx).contiguous(), False)
 
 
@@ -201,5 +210,6 @@ def attention_step2_with_rel_pos_value(attn, v, index0, index1, table, rel_idx):
 
 def attention_step2_with_rel_pos_value_v2(attn, v, index0_offsets, n_max, index1, table, rel_idx):
     attn, v, table = _prep(attn, v, table)
-    off, i1 = _i32(index0_offsets).contiguous(), _i32(index1).contiguous()
+    # the reference sizes its output by v.shape[0] too: another number of queries is an error, not a case
+    off, i1 = _offsets(index0_offsets, v.shape[0], "attention_step2_with_rel_pos_value_v2 (v has one row per query)"), _i32(index1).contiguous()
     return _PairAggregate.apply(attn, v, table, _index_from_offsets(off, i1.numel()), off, i1, _i32(rel_idx).contiguous(), v.shape[0])

@@ -82,3 +82,23 @@ def test_gpu_sync_bn_test_bodies_on_cpu_standins(name):
 
     with mock_backend.cpu_ops():
         getattr(T, name)(torch.device("cpu"))
+
+
+POINTOPS2_EDGE_TESTS = [(name, dict(case=case)) for name in ("test_every_operator_matches_the_oracle",
+                                                             "test_offsets_forms_are_bit_reproducible_and_share_the_forward_kernel",
+                                                             "test_untouched_rows_are_exactly_zero") for case in "ABCDE"] + \
+    [("test_gradient_subsets", dict(case="A")), ("test_gradient_subsets", dict(case="C")),
+     ("test_empty_pair_list", dict(nq=37)), ("test_empty_pair_list", dict(nq=0)),
+     ("test_int64_indices_give_the_bits_of_int32", dict()), ("test_strided_slices_of_one_packed_projection", dict())]
+# (test_wrappers_refuse_bad_arguments_before_any_launch is not in the list: the stand-ins do not validate dtypes and shapes; it
+#  runs on the host emulation of the real entry points, tests/test_host_emulation_cpu.py)
+
+
+@pytest.mark.parametrize("name,kw", POINTOPS2_EDGE_TESTS, ids=[f"{n}-{'-'.join(str(v) for v in k.values())}" for n, k in POINTOPS2_EDGE_TESTS])
+def test_gpu_pointops2_edge_test_bodies_on_cpu_standins(name, kw):
+    """tests/test_gpu_pointops2_edges.py: its case builder, its float64 references and every assertion, with the pair operators
+    on their oracle stand-ins (the wrappers of pointops2_api are the real ones)"""
+    import test_gpu_pointops2_edges as T
+
+    with mock_backend.cpu_ops():
+        getattr(T, name)(torch.device("cpu"), **kw)

@@ -271,6 +271,26 @@ def test_gpu_kernel_test_bodies_on_the_host_emulation(name, kw, monkeypatch):
         fn(torch.device("cpu"), **kw)
 
 
+def _pointops2_edge_tests():
+    from test_gpu_tests_dry_run_cpu import POINTOPS2_EDGE_TESTS
+
+    return POINTOPS2_EDGE_TESTS + [("test_wrappers_refuse_bad_arguments_before_any_launch", dict())]
+
+
+@pytest.mark.parametrize("name,kw", _pointops2_edge_tests(), ids=[f"{n}-{'-'.join(str(v) for v in k.values())}" for n, k in _pointops2_edge_tests()])
+def test_gpu_pointops2_edge_test_bodies_on_the_host_emulation(name, kw):
+    """tests/test_gpu_pointops2_edges.py, bodies unchanged, on the host emulation of csrc/pointops2.hip (no LDS, no wave
+    intrinsics: one fiber per thread, atomics in program order): ragged, degenerate and empty pair lists, every gradient subset
+    and the entry points' clears run the real kernel source on the CPU in every CPU run."""
+    import emu_backend
+    import test_gpu_pointops2_edges as T
+
+    if not emu_backend.available():
+        pytest.skip("no host clang++ under /opt/rocm")
+    with emu_backend.emulated_ops():
+        getattr(T, name)(torch.device("cpu"), **kw)
+
+
 def test_segmented_duplicate_merge_on_the_emulated_segment_kernel(monkeypatch):
     """functional._merge_duplicate_rows on the REAL ptc_segment_csr_fwd kernel (emulated) equals a per-row loop, fp32 and bf16 gradients."""
     import emu_backend
