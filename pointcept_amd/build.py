@@ -51,6 +51,7 @@ HIP_SOURCES = [
     "block_exec.hip",
     "mlp.hip",
     "cluster_agg.hip",
+    "cell_grid.hip",
     "pg_cluster.hip",
     "msc.hip",
     "cac.hip",

@@ -30,46 +30,45 @@
 // NaN to every entry of a head whose bound reaches 2^18 (a 2x margin over the fp32 rounding of the bound): out of range is a loud
 // NaN in the gradient, never a silent wrap.
 
-typedef __attribute__((ext_vector_type(4))) float ar_f32x4;
+#include "mma.h"
 
 #define AR32_FIX_SCALE 17592186044416.f   // 2^44
 #define AR32_FIX_LIMIT 262144.f           // 2^18: largest head sum of |dS| converted (the int64 range is 2^63 / 2^44 = 2^19)
 
-__device__ __forceinline__ ar_f32x4 ar32_mfma(float a, float b, ar_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ ar_f32x4 ar32_splat(float v) { return (ar_f32x4){v, v, v, v}; }
+__device__ __forceinline__ f32x4 ar32_splat(float v) { return (f32x4){v, v, v, v}; }
 // the float4 [4 g, 4 g + 4) of a 16-float row (zero when !valid)
-__device__ __forceinline__ ar_f32x4 ar32_ld(const float* __restrict__ row, int g, bool valid) {
-  return valid ? *reinterpret_cast<const ar_f32x4*>(row + 4 * g) : ar32_splat(0.f);
+__device__ __forceinline__ f32x4 ar32_ld(const float* __restrict__ row, int g, bool valid) {
+  return valid ? *reinterpret_cast<const f32x4*>(row + 4 * g) : ar32_splat(0.f);
 }
 // stationary x streamed over head_dim 16: D[i][j] += sum_d A-row i [d] * B-row j [d] (both operands float4 [4 g, 4 g + 4) of a row)
-__device__ __forceinline__ ar_f32x4 ar32_dot16(ar_f32x4 a, ar_f32x4 b, ar_f32x4 c) {
-  c = ar32_mfma(a[0], b[0], c);
-  c = ar32_mfma(a[1], b[1], c);
-  c = ar32_mfma(a[2], b[2], c);
-  return ar32_mfma(a[3], b[3], c);
+__device__ __forceinline__ f32x4 ar32_dot16(f32x4 a, f32x4 b, f32x4 c) {
+  c = ptc_mfma_f32_4(a[0], b[0], c);
+  c = ptc_mfma_f32_4(a[1], b[1], c);
+  c = ptc_mfma_f32_4(a[2], b[2], c);
+  return ptc_mfma_f32_4(a[3], b[3], c);
 }
 // sum over the 16 streamed rows of a tile: D[ch][j] += sum_r img[base + 4 k + r][ch] * w[r]  (lane = ch + 16 k reads the column)
-__device__ __forceinline__ ar_f32x4 ar32_acc16(const float* img, int base, int lane, ar_f32x4 w, ar_f32x4 c) {
+__device__ __forceinline__ f32x4 ar32_acc16(const float* img, int base, int lane, f32x4 w, f32x4 c) {
   const float* col = img + (size_t)(base + 4 * (lane >> 4)) * 16 + (lane & 15);
-  c = ar32_mfma(col[0], w[0], c);
-  c = ar32_mfma(col[16], w[1], c);
-  c = ar32_mfma(col[32], w[2], c);
-  return ar32_mfma(col[48], w[3], c);
+  c = ptc_mfma_f32_4(col[0], w[0], c);
+  c = ptc_mfma_f32_4(col[16], w[1], c);
+  c = ptc_mfma_f32_4(col[32], w[2], c);
+  return ptc_mfma_f32_4(col[48], w[3], c);
 }
 // rows [0, Lp) of a [*, 16] fp32 source with the given row stride into a dense [Lp][16] image (zeros beyond L)
 __device__ __forceinline__ void ar32_stage(const float* __restrict__ src, int64_t row_stride, int L, int Lp, float* img) {
   for (int i = threadIdx.x; i < Lp * 4; i += AR_THREADS) {
     const int row = i >> 2, part = i & 3;
-    ar_f32x4 v = ar32_splat(0.f);
-    if (row < L) v = *reinterpret_cast<const ar_f32x4*>(src + (int64_t)row * row_stride + 4 * part);
-    *reinterpret_cast<ar_f32x4*>(img + i * 4) = v;
+    f32x4 v = ar32_splat(0.f);
+    if (row < L) v = *reinterpret_cast<const f32x4*>(src + (int64_t)row * row_stride + 4 * part);
+    *reinterpret_cast<f32x4*>(img + i * 4) = v;
   }
 }
 // NaN into rows [0, L) (16 floats each) and the side vector: a window longer than max_seqlen (see at_poison_rows)
 __device__ __forceinline__ void ar32_poison_rows(float* rows, int64_t row_stride, int L, float* side) {
   const float nan = __uint_as_float(0x7FC00000u);
   for (int i = threadIdx.x; i < L * 4; i += AR_THREADS) {
-    *reinterpret_cast<ar_f32x4*>(rows + (int64_t)(i >> 2) * row_stride + 4 * (i & 3)) = ar32_splat(nan);
+    *reinterpret_cast<f32x4*>(rows + (int64_t)(i >> 2) * row_stride + 4 * (i & 3)) = ar32_splat(nan);
     if (side && (i & 3) == 0) side[i >> 2] = nan;
   }
 }
@@ -111,15 +110,15 @@ attn_rpe_fwd_f32_kernel(const float* __restrict__ qkv, const int32_t* __restrict
   const float* tb = tl + B;
   for (int qt = wave; qt < (Lp >> 4); qt += AT_WAVES) {
     const int q = qt * 16 + j;
-    const ar_f32x4 qf = ar32_ld(qkv + qkv_off(a + q, 0, H, head), g, q < L) * c;
+    const f32x4 qf = ar32_ld(qkv + qkv_off(a + q, 0, H, head), g, q < L) * c;
     const uint2 qc = coords[q];
     const int qx = (int)(qc.x & 0xffffu), qy = (int)(qc.x >> 16), qz = (int)qc.y;
-    ar_f32x4 acc0 = ar32_splat(0.f), acc1 = ar32_splat(0.f);
+    f32x4 acc0 = ar32_splat(0.f), acc1 = ar32_splat(0.f);
     float m = -INFINITY, l = 0.f;
     for (int kt = 0; kt < Lp; kt += 32) {
-      ar_f32x4 s[2];
-      s[0] = ar32_dot16(*reinterpret_cast<const ar_f32x4*>(Ksm + (size_t)(kt + j) * 16 + 4 * g), qf, ar32_splat(0.f));
-      s[1] = ar32_dot16(*reinterpret_cast<const ar_f32x4*>(Ksm + (size_t)(kt + 16 + j) * 16 + 4 * g), qf, ar32_splat(0.f));
+      f32x4 s[2];
+      s[0] = ar32_dot16(*reinterpret_cast<const f32x4*>(Ksm + (size_t)(kt + j) * 16 + 4 * g), qf, ar32_splat(0.f));
+      s[1] = ar32_dot16(*reinterpret_cast<const f32x4*>(Ksm + (size_t)(kt + 16 + j) * 16 + 4 * g), qf, ar32_splat(0.f));
       float mt = -INFINITY;
 #pragma unroll
       for (int h = 0; h < 2; ++h)
@@ -139,7 +138,7 @@ attn_rpe_fwd_f32_kernel(const float* __restrict__ qkv, const int32_t* __restrict
       acc0 *= alpha;
       acc1 *= alpha;
       l *= alpha;
-      ar_f32x4 p[2];
+      f32x4 p[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -153,7 +152,7 @@ attn_rpe_fwd_f32_kernel(const float* __restrict__ qkv, const int32_t* __restrict
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
     if (q < L) {
-      *reinterpret_cast<ar_f32x4*>(out + ((int64_t)(a + q) * H + head) * 16 + 4 * g) = (acc0 + acc1) * (1.f / l);
+      *reinterpret_cast<f32x4*>(out + ((int64_t)(a + q) * H + head) * 16 + 4 * g) = (acc0 + acc1) * (1.f / l);
       if (g == 0) lse[(int64_t)head * total + a + q] = m * AT_LN2 + __logf(l);
     }
   }
@@ -200,9 +199,9 @@ attn_rpe_bwd_dq_f32_kernel(const float* __restrict__ qkv, const float* __restric
   for (int qt = wave; qt < (Lp >> 4); qt += AT_WAVES) {
     const int q = qt * 16 + j;
     const bool qv = q < L;
-    const ar_f32x4 qf = ar32_ld(qkv + qkv_off(a + q, 0, H, head), g, qv) * c;
+    const f32x4 qf = ar32_ld(qkv + qkv_off(a + q, 0, H, head), g, qv) * c;
     const int64_t orow = ((int64_t)(a + q) * H + head) * 16;
-    const ar_f32x4 dof = ar32_ld(dout + orow, g, qv), of = ar32_ld(out + orow, g, qv);
+    const f32x4 dof = ar32_ld(dout + orow, g, qv), of = ar32_ld(out + orow, g, qv);
     float dl = dof[0] * of[0] + dof[1] * of[1] + dof[2] * of[2] + dof[3] * of[3];
     dl += __shfl_xor(dl, 16, 64);
     dl += __shfl_xor(dl, 32, 64);
@@ -210,11 +209,11 @@ attn_rpe_bwd_dq_f32_kernel(const float* __restrict__ qkv, const float* __restric
     if (qv && g == 0) delta[(int64_t)head * total + a + q] = dl;
     const uint2 qc = coords[q];
     const int qx = (int)(qc.x & 0xffffu), qy = (int)(qc.x >> 16), qz = (int)qc.y;
-    ar_f32x4 acc0 = ar32_splat(0.f), acc1 = ar32_splat(0.f);
+    f32x4 acc0 = ar32_splat(0.f), acc1 = ar32_splat(0.f);
     for (int kt = 0; kt < Lp; kt += 16) {
-      const ar_f32x4 s = ar32_dot16(*reinterpret_cast<const ar_f32x4*>(Ksm + (size_t)(kt + j) * 16 + 4 * g), qf, ar32_splat(-l2));
-      const ar_f32x4 dp = ar32_dot16(*reinterpret_cast<const ar_f32x4*>(Vsm + (size_t)(kt + j) * 16 + 4 * g), dof, ar32_splat(-dl));
-      ar_f32x4 ds;
+      const f32x4 s = ar32_dot16(*reinterpret_cast<const f32x4*>(Ksm + (size_t)(kt + j) * 16 + 4 * g), qf, ar32_splat(-l2));
+      const f32x4 dp = ar32_dot16(*reinterpret_cast<const f32x4*>(Vsm + (size_t)(kt + j) * 16 + 4 * g), dof, ar32_splat(-dl));
+      f32x4 ds;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kt + 4 * g + r;
@@ -233,7 +232,7 @@ attn_rpe_bwd_dq_f32_kernel(const float* __restrict__ qkv, const float* __restric
       if ((kt & 16) == 0) acc0 = ar32_acc16(Ksm, kt, lane, ds, acc0);
       else acc1 = ar32_acc16(Ksm, kt, lane, ds, acc1);
     }
-    if (qv) *reinterpret_cast<ar_f32x4*>(dqkv + qkv_off(a + q, 0, H, head) + 4 * g) = (acc0 + acc1) * scale;
+    if (qv) *reinterpret_cast<f32x4*>(dqkv + qkv_off(a + q, 0, H, head) + 4 * g) = (acc0 + acc1) * scale;
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) asum += __shfl_xor(asum, o, 64);
@@ -298,16 +297,16 @@ attn_rpe_bwd_dkv_f32_kernel(const float* __restrict__ qkv, const float* __restri
   for (int kt = wave; kt < (Lp >> 4); kt += AT_WAVES) {
     const int key = kt * 16 + j;
     const bool kv = key < L;
-    const ar_f32x4 kf = ar32_ld(qkv + qkv_off(a + key, 1, H, head), g, kv) * c;
-    const ar_f32x4 vf = ar32_ld(qkv + qkv_off(a + key, 2, H, head), g, kv);
+    const f32x4 kf = ar32_ld(qkv + qkv_off(a + key, 1, H, head), g, kv) * c;
+    const f32x4 vf = ar32_ld(qkv + qkv_off(a + key, 2, H, head), g, kv);
     const uint2 kc = coords[key];
-    ar_f32x4 dv = ar32_splat(0.f), dk = ar32_splat(0.f);
+    f32x4 dv = ar32_splat(0.f), dk = ar32_splat(0.f);
     for (int qt = 0; qt < Lp; qt += 16) {
-      const ar_f32x4 nl2 = -*reinterpret_cast<const ar_f32x4*>(l2s + qt + 4 * g);
-      const ar_f32x4 ndl = -*reinterpret_cast<const ar_f32x4*>(dls + qt + 4 * g);
-      const ar_f32x4 s = ar32_dot16(*reinterpret_cast<const ar_f32x4*>(Qsm + (size_t)(qt + j) * 16 + 4 * g), kf, nl2);
-      const ar_f32x4 dp = ar32_dot16(*reinterpret_cast<const ar_f32x4*>(dOsm + (size_t)(qt + j) * 16 + 4 * g), vf, ndl);
-      ar_f32x4 p, ds;
+      const f32x4 nl2 = -*reinterpret_cast<const f32x4*>(l2s + qt + 4 * g);
+      const f32x4 ndl = -*reinterpret_cast<const f32x4*>(dls + qt + 4 * g);
+      const f32x4 s = ar32_dot16(*reinterpret_cast<const f32x4*>(Qsm + (size_t)(qt + j) * 16 + 4 * g), kf, nl2);
+      const f32x4 dp = ar32_dot16(*reinterpret_cast<const f32x4*>(dOsm + (size_t)(qt + j) * 16 + 4 * g), vf, ndl);
+      f32x4 p, ds;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const uint2 qc = coords[qt + 4 * g + r];                 // the QUERY of this element; the lane's key is kc
@@ -320,8 +319,8 @@ attn_rpe_bwd_dkv_f32_kernel(const float* __restrict__ qkv, const float* __restri
       dk = ar32_acc16(Qsm, qt, lane, ds, dk);
     }
     if (kv) {
-      *reinterpret_cast<ar_f32x4*>(dqkv + qkv_off(a + key, 1, H, head) + 4 * g) = dk * scale;
-      *reinterpret_cast<ar_f32x4*>(dqkv + qkv_off(a + key, 2, H, head) + 4 * g) = dv;
+      *reinterpret_cast<f32x4*>(dqkv + qkv_off(a + key, 1, H, head) + 4 * g) = dk * scale;
+      *reinterpret_cast<f32x4*>(dqkv + qkv_off(a + key, 2, H, head) + 4 * g) = dv;
     }
   }
 }

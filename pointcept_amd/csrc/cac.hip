@@ -14,16 +14,13 @@
 // workgroup over a FIXED row range in row order, written as a partial, and the partials are added in index order by a finishing
 // kernel -- the results are the same bits on every run.  Nothing of size [N, K] is saved between forward and backward: the
 // backward kernels recompute the softmax rows.
-#include "ptc_common.h"
+#include "mma.h"
 
 #define CAC_ROWS 32          // rows per tile
 #define CAC_THREADS 256
 #define CAC_MAX_K 256
 #define CAC_MAX_C 128
 #define CAC_NORM_EPS 1e-12f  // F.normalize's clamp
-
-typedef __attribute__((ext_vector_type(4))) float cac_f32x4;
-__device__ __forceinline__ cac_f32x4 cac_mfma(float a, float b, cac_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 static inline int cac_kp(int k) { return (k + 15) / 16 * 16; }
 // LDS row strides (in floats) of a [32][dim] tile, dim a multiple of 16.  ld_m: the tile's rows are the M side of the product (lane i
@@ -73,9 +70,9 @@ __device__ __forceinline__ void cac_stage_rows(const float* __restrict__ x, int 
   const int c4n = C >> 2;
   for (int v = threadIdx.x; v < CAC_ROWS * c4n; v += CAC_THREADS) {
     const int r = v / c4n, c4 = (v - r * c4n) << 2;
-    cac_f32x4 val = {0.f, 0.f, 0.f, 0.f};
-    if (t0 + r < r1) val = *reinterpret_cast<const cac_f32x4*>(x + (t0 + r) * C + c4);
-    *reinterpret_cast<cac_f32x4*>(tile + r * ld + c4) = val;
+    f32x4 val = {0.f, 0.f, 0.f, 0.f};
+    if (t0 + r < r1) val = *reinterpret_cast<const f32x4*>(x + (t0 + r) * C + c4);
+    *reinterpret_cast<f32x4*>(tile + r * ld + c4) = val;
   }
 }
 
@@ -101,9 +98,9 @@ cac_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ logit
   const int64_t per = ((end - beg + P - 1) / P + CAC_ROWS - 1) / CAC_ROWS * CAC_ROWS;
   const int64_t r0 = beg + (int64_t)j * per, r1 = (r0 + per < end) ? r0 + per : end;
   const int CT = C >> 4, ntile = (Kp >> 4) * CT;
-  cac_f32x4 acc[MAXT];
+  f32x4 acc[MAXT];
 #pragma unroll
-  for (int t = 0; t < MAXT; ++t) acc[t] = (cac_f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < MAXT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   double colsum = 0.0;          // the weight sums in double: exact to the rounding of the result, whatever the range's length
   int passed = 0;
   if (tid == 0) cnt[0] = 0;
@@ -138,7 +135,7 @@ cac_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ logit
         const float* a = Wl + lk * ldw + kt * 16 + li;
         const float* b = Xl + lk * ldx + ct * 16 + li;
 #pragma unroll
-        for (int r4 = 0; r4 < CAC_ROWS / 4; ++r4) acc[t] = cac_mfma(a[4 * r4 * ldw], b[4 * r4 * ldx], acc[t]);
+        for (int r4 = 0; r4 < CAC_ROWS / 4; ++r4) acc[t] = ptc_mfma_f32_4(a[4 * r4 * ldw], b[4 * r4 * ldx], acc[t]);
       }
     }
     __syncthreads();
@@ -195,12 +192,12 @@ cac_pool_bwd_hard_kernel(const int64_t* __restrict__ target, int64_t n, int K, i
   const int64_t i = idx / c4n;
   const int c4 = (int)(idx - i * c4n) << 2;
   const int64_t t = target[i];
-  cac_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
   if (t >= 0 && t < K) {
     const float inv = 1.f / (wsum[t] + eps);
-    v = *reinterpret_cast<const cac_f32x4*>(dproto + t * C + c4) * inv;
+    v = *reinterpret_cast<const f32x4*>(dproto + t * C + c4) * inv;
   }
-  *reinterpret_cast<cac_f32x4*>(dx + i * C + c4) = v;
+  *reinterpret_cast<f32x4*>(dx + i * C + c4) = v;
 }
 
 // soft: grid (T, S), workgroup (t, s) walks the 32-row tiles t, t + T, ... of segment s.
@@ -240,8 +237,8 @@ cac_pool_bwd_soft_kernel(const float* __restrict__ x, const float* __restrict__ 
         const float* a = Xl + (mt * 16 + li) * ldx + lk;
         const bool bk = nt * 16 + li < K;
         const float* b = dps + (bk ? nt * 16 + li : 0) * C + lk;
-        cac_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int r4 = 0; r4 < C / 4; ++r4) acc = cac_mfma(a[4 * r4], bk ? b[4 * r4] : 0.f, acc);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int r4 = 0; r4 < C / 4; ++r4) acc = ptc_mfma_f32_4(a[4 * r4], bk ? b[4 * r4] : 0.f, acc);
 #pragma unroll
         for (int e = 0; e < 4; ++e) Gl[(mt * 16 + 4 * lk + e) * ldk + nt * 16 + li] = acc[e];
       }
@@ -272,10 +269,10 @@ cac_pool_bwd_soft_kernel(const float* __restrict__ x, const float* __restrict__ 
       const int mt = id & 1, nt = id >> 1;
       const float* a = Gl + (mt * 16 + li) * ldk + lk;
       const float* b = dps + nt * 16 + li;
-      cac_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       for (int r4 = 0; r4 < Kp / 4; ++r4) {
         const int k = 4 * r4 + lk;
-        acc = cac_mfma(a[4 * r4], k < K ? b[k * C] : 0.f, acc);
+        acc = ptc_mfma_f32_4(a[4 * r4], k < K ? b[k * C] : 0.f, acc);
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -344,8 +341,8 @@ cac_cos_fwd_kernel(const float* __restrict__ x, const float* __restrict__ phat, 
       const int mt = id & 1, nt = id >> 1;
       const float* a = Xl + (mt * 16 + li) * ldx + lk;
       const float* b = ph + (nt * 16 + li) * C + lk;
-      cac_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      for (int r4 = 0; r4 < C / 4; ++r4) acc = cac_mfma(a[4 * r4], b[4 * r4], acc);
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      for (int r4 = 0; r4 < C / 4; ++r4) acc = ptc_mfma_f32_4(a[4 * r4], b[4 * r4], acc);
       const int col = nt * 16 + li;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -380,9 +377,9 @@ cac_cos_bwd_kernel(const float* __restrict__ x, const float* __restrict__ phat, 
   const int64_t r0 = beg + (int64_t)j * per, r1 = (r0 + per < end) ? r0 + per : end;
   const float* ph = phat + (int64_t)s * Kp * C;
   const int CT = C >> 4, ntile = (Kp >> 4) * CT;
-  cac_f32x4 acc[MAXT];
+  f32x4 acc[MAXT];
 #pragma unroll
-  for (int t = 0; t < MAXT; ++t) acc[t] = (cac_f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < MAXT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int row = tid >> 3, q = tid & 7;
   for (int64_t t0 = r0; t0 < r1; t0 += CAC_ROWS) {
     cac_stage_rows(x, C, t0, r1, Xl, ldx);
@@ -398,8 +395,8 @@ cac_cos_bwd_kernel(const float* __restrict__ x, const float* __restrict__ phat, 
       const int mt = id & 1, nt = id >> 1;
       const float* a = Dl + (mt * 16 + li) * ldk + lk;
       const float* b = ph + lk * C + nt * 16 + li;
-      cac_f32x4 y = {0.f, 0.f, 0.f, 0.f};
-      for (int r4 = 0; r4 < Kp / 4; ++r4) y = cac_mfma(a[4 * r4], b[4 * r4 * C], y);
+      f32x4 y = {0.f, 0.f, 0.f, 0.f};
+      for (int r4 = 0; r4 < Kp / 4; ++r4) y = ptc_mfma_f32_4(a[4 * r4], b[4 * r4 * C], y);
 #pragma unroll
       for (int e = 0; e < 4; ++e) Yl[(mt * 16 + 4 * lk + e) * ldx + nt * 16 + li] = y[e];
     }
@@ -420,7 +417,7 @@ cac_cos_bwd_kernel(const float* __restrict__ x, const float* __restrict__ phat, 
         const float* a = Dl + lk * ldk + kt * 16 + li;
         const float* b = Xl + lk * ldx + ct * 16 + li;
 #pragma unroll
-        for (int r4 = 0; r4 < CAC_ROWS / 4; ++r4) acc[t] = cac_mfma(a[4 * r4 * ldk], b[4 * r4 * ldx], acc[t]);
+        for (int r4 = 0; r4 < CAC_ROWS / 4; ++r4) acc[t] = ptc_mfma_f32_4(a[4 * r4 * ldk], b[4 * r4 * ldx], acc[t]);
       }
     }
     __syncthreads();
@@ -619,12 +616,11 @@ static CacPoolWs cac_pool_ws(void* base, int64_t n, int s, int k, int c) {
   CacPoolWs W;
   const int Kp = cac_kp(k);
   W.P = cac_parts(n, s);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { void* p = (char*)base + o; o += ptc_align_up(bytes, 256); return p; };
-  W.part = (float*)take((size_t)s * W.P * Kp * c * 4);
-  W.wpart = (double*)take((size_t)s * W.P * Kp * 8);
-  W.ppart = (int*)take((size_t)s * W.P * 4);
-  W.total = o;
+  PtcArena A(base);          // s, P >= 1 and Kp, c >= 16: no piece is empty
+  W.part = A.take_as<float>((size_t)s * W.P * Kp * c * 4);
+  W.wpart = A.take_as<double>((size_t)s * W.P * Kp * 8);
+  W.ppart = A.take_as<int>((size_t)s * W.P * 4);
+  W.total = A.total;
   return W;
 }
 
@@ -695,12 +691,11 @@ static CacCosWs cac_cos_ws(void* base, int64_t n, int s, int k, int c) {
   CacCosWs W;
   const int Kp = cac_kp(k);
   W.P = cac_parts(n, s);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { void* p = (char*)base + o; o += ptc_align_up(bytes, 256); return p; };
-  W.phat = (float*)take((size_t)s * Kp * c * 4);
-  W.pnorm = (float*)take((size_t)s * Kp * 4);
-  W.part = (float*)take((size_t)s * W.P * Kp * c * 4);
-  W.total = o;
+  PtcArena A(base);          // no piece is empty, as above
+  W.phat = A.take_as<float>((size_t)s * Kp * c * 4);
+  W.pnorm = A.take_as<float>((size_t)s * Kp * 4);
+  W.part = A.take_as<float>((size_t)s * W.P * Kp * c * 4);
+  W.total = A.total;
   return W;
 }
 

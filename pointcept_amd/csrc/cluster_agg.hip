@@ -84,13 +84,6 @@ __device__ __forceinline__ void ca_st4(f16_t* p, const float (&f)[4]) {
   *reinterpret_cast<uint2*>(p) = q;
 }
 
-// order-preserving map float -> uint32 (unsigned compare = float compare; 0 is below every encoded value)
-__device__ __forceinline__ uint32_t ca_enc(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ca_dec(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 // softmax of the L logits of row n (fp32)
 template <typename T>
 __device__ __forceinline__ void ca_softmax(const T* __restrict__ a, int64_t n, int L, float (&p)[CA_MAX_LEVELS]) {
@@ -251,7 +244,7 @@ __global__ void __launch_bounds__(256) ca_max_kernel(CaLevels P, int64_t nc, uin
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nc / 4; i += stride) {
     float f[4];
     ca_ld4(u + 4 * i, f);
-    for (int k = 0; k < 4; ++k) m = max(m, ca_enc(f[k]));
+    for (int k = 0; k < 4; ++k) m = max(m, ptc_float_enc(f[k]));
   }
   for (int o = 32; o >= 1; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
   if (ptc_lane() == 0) atomicMax(mx + l, m);    // integer maximum: independent of the update order
@@ -270,7 +263,7 @@ __global__ void __launch_bounds__(CA_THREADS) ca_agg_cluster_fwd_kernel(CaLevels
   const int64_t* perm = ca_pick(P.perm, l);
   const int64_t* ip = ca_pick(P.indptr, l);
   const int64_t beg = ip[cl], end = ip[cl + 1];
-  const float M = ca_dec(mx[l]);
+  const float M = ptc_float_dec(mx[l]);
   const int j = threadIdx.x % Y.G, s = threadIdx.x / Y.G;
   const bool act = j < Y.cg;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // den[4], num[4]
@@ -381,7 +374,7 @@ __global__ void __launch_bounds__(CA_THREADS) ca_agg_cluster_bwd_kernel(CaLevels
   const int64_t* ip = ca_pick(P.indptr, l);
   const int64_t beg = ip[cl], end = ip[cl + 1];
   const uint32_t Menc = mx[l];
-  const float M = ca_dec(Menc);
+  const float M = ptc_float_dec(Menc);
   const int j = threadIdx.x % Y.G, s = threadIdx.x / Y.G;
   const bool act = j < Y.cg;
   float ds[4] = {0.f, 0.f, 0.f, 0.f};
@@ -416,7 +409,7 @@ __global__ void __launch_bounds__(CA_THREADS) ca_agg_cluster_bwd_kernel(CaLevels
         gv[k] = gq[k] * e;
         gu[k] = gv[k] * (fv[k] - sv[k]);
         sum += gu[k];
-        n_max += ca_enc(fu[k]) == Menc;
+        n_max += ptc_float_enc(fu[k]) == Menc;
       }
       ca_st4(dv + m * c + 4 * j, gv);
       ca_st4(du + m * c + 4 * j, gu);
@@ -485,12 +478,12 @@ __global__ void __launch_bounds__(CA_THREADS) ca_agg_max_fix_kernel(CaLevels P, 
     float fu[4];
     ca_ld4(u + m * c + 4 * j, fu);
     bool hit = false;
-    for (int k = 0; k < 4; ++k) hit |= ca_enc(fu[k]) == Menc;
+    for (int k = 0; k < 4; ++k) hit |= ptc_float_enc(fu[k]) == Menc;
     if (!hit) continue;
     float gu[4];
     ca_ld4(du + m * c + 4 * j, gu);
     for (int k = 0; k < 4; ++k)
-      if (ca_enc(fu[k]) == Menc) gu[k] += ql;
+      if (ptc_float_enc(fu[k]) == Menc) gu[k] += ql;
     ca_st4(du + m * c + 4 * j, gu);
   }
 }

@@ -9,6 +9,10 @@ typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
+// one v_mfma_f32_16x16x4_f32: a, b one scalar per lane (A[i][k] in lane i + 16 k, B[k][j] in lane j + 16 k), D[i][j] in lane
+// j + 16 (i / 4), element i % 4
+__device__ __forceinline__ f32x4 ptc_mfma_f32_4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {
   static constexpr int KS = 32;   // channels per super-step
@@ -34,10 +38,10 @@ template <> struct Mma<float> {
   using frag = f32x4;
   static __device__ __forceinline__ frag zero() { frag z = {0.f, 0.f, 0.f, 0.f}; return z; }
   static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
+    c = ptc_mfma_f32_4(a[0], b[0], c);
+    c = ptc_mfma_f32_4(a[1], b[1], c);
+    c = ptc_mfma_f32_4(a[2], b[2], c);
+    c = ptc_mfma_f32_4(a[3], b[3], c);
     return c;
   }
 };

@@ -18,31 +18,14 @@
 //    dA = (softmax - I) B / (P t) and dB = (softmax - I)^T A / (P t), then applies the Jacobian of the normalisation.  Rows matched
 //    several times are summed after a stable sort by row, in that order.  No float atomics; every reduction has a fixed order, so
 //    forward and backward are bit-reproducible.
+#include "cell_grid.h"
 #include "mma.h"
 
 #define MSC_THREADS 256
 #define MSC_KMAX 8
-#define MSC_CELL_MAX 65533           // cell fields hold 0..65535; neighbours reach -1..65534
-#define MSC_EXTENT_CELLS 60000.0
-#define MSC_EDGE_MARGIN 1.0001       // cell edge >= max_radius * (1 + 1e-4): the fp32 rounding of d2 and of the root never reaches past one cell
 
 namespace {
 
-__device__ __forceinline__ uint32_t msc_enc(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float msc_dec(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-__device__ __forceinline__ bool msc_finite3(float x, float y, float z) {
-  return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
-// pointops.hip's po_dist2
-__device__ __forceinline__ float msc_dist2(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-  return (xx + yy) + zz;
-}
 // smallest i with p < ends[i]; b when p >= ends[b-1]
 __device__ __forceinline__ int msc_scene_of(const int* __restrict__ ends, int b, int64_t p) {
   int lo = 0, hi = b;
@@ -57,90 +40,26 @@ int msc_grid1(int64_t n) { return (int)ptc_cdiv(n > 0 ? n : 1, MSC_THREADS); }
 // ---------------------------------------------------------------------------------------------------------------------------------
 // 1. matching
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct MscGrid {
-  double mn[3];
-  double edge;
-};
-
-// componentwise min / max of the finite rows (order-preserving integer codes, integer atomics); hi == 0: no finite row seen
-__global__ void msc_bounds_kernel(const float* __restrict__ xyz, int64_t n, uint32_t* __restrict__ mm) {
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
-    if (!msc_finite3(x, y, z)) continue;
-    const uint32_t e[3] = {msc_enc(x), msc_enc(y), msc_enc(z)};
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = e[a] < lo[a] ? e[a] : lo[a];
-      hi[a] = e[a] > hi[a] ? e[a] : hi[a];
-    }
-  }
-  for (int a = 0; a < 3; ++a) {
-    if (hi[a] == 0u) continue;
-    atomicMin(mm + a, lo[a]);
-    atomicMax(mm + 3 + a, hi[a]);
-  }
-}
-
-__global__ void msc_grid_params_kernel(const uint32_t* __restrict__ mm, double radius, MscGrid* __restrict__ g, int32_t* __restrict__ stats) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double ext = 0.0;
-  const bool any = mm[3] != 0u;
-  for (int a = 0; a < 3; ++a) {
-    const double lo = any ? (double)msc_dec(mm[a]) : 0.0, hi = any ? (double)msc_dec(mm[3 + a]) : 0.0;
-    g->mn[a] = lo;
-    ext = hi - lo > ext ? hi - lo : ext;
-  }
-  double edge = radius * MSC_EDGE_MARGIN;
-  if (ext / edge > MSC_EXTENT_CELLS) edge = ext / MSC_EXTENT_CELLS;
-  g->edge = edge;
-  stats[0] = 0;
-  stats[1] = 0;
-}
-
-__device__ __forceinline__ int msc_cell(float v, double mn, double edge) {
-  double c = floor(((double)v - mn) / edge);
-  c = c < 0.0 ? 0.0 : (c > (double)MSC_CELL_MAX ? (double)MSC_CELL_MAX : c);
-  return (int)c;
-}
-__device__ __forceinline__ int64_t msc_key(int b, int cx, int cy, int cz) {
-  return ((int64_t)b << 48) | ((int64_t)cz << 32) | ((int64_t)cy << 16) | (int64_t)cx;
-}
-
-// key of a row of `xyz` (scene from `offset`); scene `b` = matches nothing (non-finite, or beyond the last offset)
+// key of a row of `xyz` (scene from `offset`); scene `b` = matches nothing (non-finite, or beyond the last offset).  Also zeroes the two
+// counters that msc_match_kernel adds to.
 __global__ void msc_keys_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ offset, int b, int64_t n,
-                                const MscGrid* __restrict__ g, int64_t* __restrict__ keys) {
+                                const PtcCellGrid* __restrict__ g, int64_t* __restrict__ keys, int32_t* __restrict__ stats) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (i == 0) { stats[0] = 0; stats[1] = 0; }
   const float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
   const int s = msc_scene_of(offset, b, i);
-  if (!msc_finite3(x, y, z) || s >= b) {
-    keys[i] = msc_key(b, 0, 0, 0);
+  if (!ptc_finite3(x, y, z) || s >= b) {
+    keys[i] = ptc_cell_key(b, 0, 0, 0);
     return;
   }
   const double e = g->edge;
-  keys[i] = msc_key(s, msc_cell(x, g->mn[0], e), msc_cell(y, g->mn[1], e), msc_cell(z, g->mn[2], e));
-}
-
-// sxyz[p] = (xyz[order[p]], bits of order[p])
-__global__ void msc_sorted_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ order, int64_t n, float4* __restrict__ sxyz) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  const int64_t k = order[p];
-  sxyz[p] = make_float4(xyz[k * 3], xyz[k * 3 + 1], xyz[k * 3 + 2], __int_as_float((int)k));
-}
-
-__device__ __forceinline__ int64_t msc_lower_bound(const int64_t* __restrict__ a, int64_t lo, int64_t hi, int64_t key) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
+  keys[i] = ptc_cell_key(s, ptc_cell(x, g->mn[0], e), ptc_cell(y, g->mn[1], e), ptc_cell(z, g->mn[2], e));
 }
 
 // one query per thread: the 9 x-runs of its 27 cells, candidates kept as a register list ascending by (d2, index)
 __global__ void __launch_bounds__(MSC_THREADS)
-msc_match_kernel(const float* __restrict__ qxyz, const int32_t* __restrict__ qoffset, int b, int64_t m, const MscGrid* __restrict__ g,
+msc_match_kernel(const float* __restrict__ qxyz, const int32_t* __restrict__ qoffset, int b, int64_t m, const PtcCellGrid* __restrict__ g,
                  const int64_t* __restrict__ skeys, const float4* __restrict__ sxyz, int64_t n, int k, float radius,
                  int32_t* __restrict__ count, int32_t* __restrict__ cand, int32_t* __restrict__ stats) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -152,36 +71,29 @@ msc_match_kernel(const float* __restrict__ qxyz, const int32_t* __restrict__ qof
   if (q < m) {
     const float qx = qxyz[q * 3], qy = qxyz[q * 3 + 1], qz = qxyz[q * 3 + 2];
     const int s = msc_scene_of(qoffset, b, q);
-    if (msc_finite3(qx, qy, qz) && s < b && n > 0) {
+    if (ptc_finite3(qx, qy, qz) && s < b && n > 0) {
       const double e = g->edge;
-      const int cx = msc_cell(qx, g->mn[0], e), cy = msc_cell(qy, g->mn[1], e), cz = msc_cell(qz, g->mn[2], e);
-      for (int dz = -1; dz <= 1; ++dz) {
-        if (cz + dz < 0) continue;
-        for (int dy = -1; dy <= 1; ++dy) {
-          if (cy + dy < 0) continue;
-          const int x0 = cx > 0 ? cx - 1 : 0;
-          const int64_t lo = msc_lower_bound(skeys, 0, n, msc_key(s, x0, cy + dy, cz + dz));
-          const int64_t hi = msc_lower_bound(skeys, lo, n, msc_key(s, cx + 2, cy + dy, cz + dz));
-          for (int64_t p = lo; p < hi; ++p) {
-            const float4 c = sxyz[p];
-            const float d2 = msc_dist2(qx, qy, qz, c.x, c.y, c.z);
-            if (!((float)sqrt((double)d2) < radius)) continue;
-            const int ci = __float_as_int(c.w);
-            if (d2 < bd[MSC_KMAX - 1] || (d2 == bd[MSC_KMAX - 1] && ci < bi[MSC_KMAX - 1]) || bi[MSC_KMAX - 1] < 0) {
-              int pos = 0;
+      const int cx = ptc_cell(qx, g->mn[0], e), cy = ptc_cell(qy, g->mn[1], e), cz = ptc_cell(qz, g->mn[2], e);
+      ptc_cell_runs(skeys, n, s, cx, cy, cz, [&](int64_t lo, int64_t hi, int, int) {
+        for (int64_t p = lo; p < hi; ++p) {
+          const float4 c = sxyz[p];
+          const float d2 = ptc_dist2(qx, qy, qz, c.x, c.y, c.z);
+          if (!((float)sqrt((double)d2) < radius)) continue;
+          const int ci = __float_as_int(c.w);
+          if (d2 < bd[MSC_KMAX - 1] || (d2 == bd[MSC_KMAX - 1] && ci < bi[MSC_KMAX - 1]) || bi[MSC_KMAX - 1] < 0) {
+            int pos = 0;
 #pragma unroll
-              for (int j = 0; j < MSC_KMAX; ++j) pos += (bi[j] >= 0 && (bd[j] < d2 || (bd[j] == d2 && bi[j] < ci))) ? 1 : 0;
+            for (int j = 0; j < MSC_KMAX; ++j) pos += (bi[j] >= 0 && (bd[j] < d2 || (bd[j] == d2 && bi[j] < ci))) ? 1 : 0;
 #pragma unroll
-              for (int j = MSC_KMAX - 1; j > 0; --j)
-                if (j > pos) { bd[j] = bd[j - 1]; bi[j] = bi[j - 1]; }
+            for (int j = MSC_KMAX - 1; j > 0; --j)
+              if (j > pos) { bd[j] = bd[j - 1]; bi[j] = bi[j - 1]; }
 #pragma unroll
-              for (int j = 0; j < MSC_KMAX; ++j)
-                if (j == pos) { bd[j] = d2; bi[j] = ci; }
-              cnt += cnt < MSC_KMAX ? 1 : 0;
-            }
+            for (int j = 0; j < MSC_KMAX; ++j)
+              if (j == pos) { bd[j] = d2; bi[j] = ci; }
+            cnt += cnt < MSC_KMAX ? 1 : 0;
           }
         }
-      }
+      });
     }
     cnt = cnt < k ? cnt : k;
     count[q] = cnt;
@@ -211,21 +123,16 @@ __global__ void msc_zero_match_kernel(int64_t m, int k, int32_t* __restrict__ co
 }
 
 struct MatchLayout {
-  size_t mm, grid, keys, order, skeys, sxyz, scratch, total;
+  PtcCellGridLayout g;
+  size_t total;
 };
 MatchLayout match_layout(int64_t n) {
   MatchLayout Y;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += ptc_align_up(bytes ? bytes : 1, 256); return at; };
+  PtcArena A;
   const int64_t c = n > 0 ? n : 1;
-  Y.mm = take(6 * 4);
-  Y.grid = take(sizeof(MscGrid));
-  Y.keys = take((size_t)c * 8);
-  Y.order = take((size_t)c * 8);
-  Y.skeys = take((size_t)c * 8);
-  Y.sxyz = take((size_t)c * 16);
-  Y.scratch = take(ptc_sort_keys_workspace_bytes(c, 1));
-  Y.total = o;
+  Y.g.take_arrays(A, c);
+  Y.g.take_scratch(A, c);
+  Y.total = A.total;
   return Y;
 }
 
@@ -257,7 +164,7 @@ __global__ void msc_cell_max_kernel(const float* __restrict__ c1, int64_t n1, co
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n1 + n2; i += (int64_t)gridDim.x * blockDim.x) {
     const float* p = i < n1 ? c1 + i * 3 : c2 + (i - n1) * 3;
     for (int a = 0; a < 3; ++a) {
-      const uint32_t e = msc_enc(p[a]);
+      const uint32_t e = ptc_float_enc(p[a]);
       hi[a] = e > hi[a] ? e : hi[a];
     }
   }
@@ -276,7 +183,7 @@ __global__ void msc_patch_ids_kernel(const float* __restrict__ c1, const int32_t
   const float* p = first ? c1 + i * 3 : c2 + (i - n1) * 3;
   int s = first ? msc_scene_of(off1, b, i) : msc_scene_of(off2, b, i - n1);
   s = s < b ? s : b - 1;
-  const uint64_t nx = (uint64_t)((int64_t)msc_dec(mx[0]) + 1), ny = (uint64_t)((int64_t)msc_dec(mx[1]) + 1), nz = (uint64_t)((int64_t)msc_dec(mx[2]) + 1);
+  const uint64_t nx = (uint64_t)((int64_t)ptc_float_dec(mx[0]) + 1), ny = (uint64_t)((int64_t)ptc_float_dec(mx[1]) + 1), nz = (uint64_t)((int64_t)ptc_float_dec(mx[2]) + 1);
   // two's-complement wrap-around as the int64 tensor arithmetic of voxel_grid
   const uint64_t id = (uint64_t)(int64_t)p[0] + (uint64_t)(int64_t)p[1] * nx + (uint64_t)(int64_t)p[2] * (nx * ny) + (uint64_t)(int64_t)s * (nx * ny * nz);
   keys[i] = (int64_t)(id ^ 0x8000000000000000ull);
@@ -310,18 +217,17 @@ struct PatchLayout {
 };
 PatchLayout patch_layout(int64_t n) {
   PatchLayout Y;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += ptc_align_up(bytes ? bytes : 1, 256); return at; };
+  PtcArena A;
   const int64_t c = n > 0 ? n : 1;
-  Y.mx = take(3 * 4);
-  Y.keys = take((size_t)c * 8);
-  Y.order = take((size_t)c * 8);
-  Y.skeys = take((size_t)c * 8);
-  Y.flag = take((size_t)c * 4);
-  Y.scan = take((size_t)c * 8);
+  Y.mx = A.take(3 * 4);
+  Y.keys = A.take((size_t)c * 8);
+  Y.order = A.take((size_t)c * 8);
+  Y.skeys = A.take((size_t)c * 8);
+  Y.flag = A.take((size_t)c * 4);
+  Y.scan = A.take((size_t)c * 8);
   const size_t s1 = ptc_sort_keys_workspace_bytes(c, 1), s2 = ptc_exclusive_scan_workspace_bytes(c);
-  Y.scratch = take(s1 > s2 ? s1 : s2);
-  Y.total = o;
+  Y.scratch = A.take(s1 > s2 ? s1 : s2);
+  Y.total = A.total;
   return Y;
 }
 
@@ -337,9 +243,7 @@ PatchLayout patch_layout(int64_t n) {
 #define NCE_EPS 1e-7f
 #define NCE_MAX_P (1 << 20)          // the O(P^2) products and the one-workgroup finish are meant for P of this order, not for 2^31
 
-typedef __attribute__((ext_vector_type(4))) float nce_f32x4;
-__device__ __forceinline__ nce_f32x4 nce_splat(float v) { return (nce_f32x4){v, v, v, v}; }
-__device__ __forceinline__ nce_f32x4 nce_mfma(float a, float b, nce_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 nce_splat(float v) { return (f32x4){v, v, v, v}; }
 
 // S / t as ONE rounded product in the forward and in the backward alike: contracted into the subtraction of the lse it would differ
 // from the value the lse was built from, and exp(z - lse) of a one-column row would not be exactly 1
@@ -376,24 +280,24 @@ __device__ __forceinline__ void nce_stage(const float* __restrict__ src, int64_t
   const int per_row = LDW >> 2;
   for (int i = threadIdx.x; i < NCE_TILE * per_row; i += MSC_THREADS) {
     const int row = i / per_row, c4 = (i - row * per_row) * 4;
-    nce_f32x4 v = nce_splat(0.f);
-    if (r0 + row < P && c4 < C) v = *reinterpret_cast<const nce_f32x4*>(src + (r0 + row) * C + c4);
-    *reinterpret_cast<nce_f32x4*>(img + row * LDW + c4) = v;
+    f32x4 v = nce_splat(0.f);
+    if (r0 + row < P && c4 < C) v = *reinterpret_cast<const f32x4*>(src + (r0 + row) * C + c4);
+    *reinterpret_cast<f32x4*>(img + row * LDW + c4) = v;
   }
 }
 
 // S^T sub-tile: lane (j, g) gets S(stationary row j, streamed rows 16 t + 4 g + r), r = 0..3
 template <int CH>
-__device__ __forceinline__ nce_f32x4 nce_scores(const float* img, int LDW, int t, int j, int g, const nce_f32x4 (&stat)[CH]) {
-  nce_f32x4 s = nce_splat(0.f);
+__device__ __forceinline__ f32x4 nce_scores(const float* img, int LDW, int t, int j, int g, const f32x4 (&stat)[CH]) {
+  f32x4 s = nce_splat(0.f);
   const float* row = img + (16 * t + j) * LDW + 4 * g;
 #pragma unroll
   for (int ch = 0; ch < CH; ++ch) {
-    const nce_f32x4 a = *reinterpret_cast<const nce_f32x4*>(row + 16 * ch);
-    s = nce_mfma(a[0], stat[ch][0], s);
-    s = nce_mfma(a[1], stat[ch][1], s);
-    s = nce_mfma(a[2], stat[ch][2], s);
-    s = nce_mfma(a[3], stat[ch][3], s);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(row + 16 * ch);
+    s = ptc_mfma_f32_4(a[0], stat[ch][0], s);
+    s = ptc_mfma_f32_4(a[1], stat[ch][1], s);
+    s = ptc_mfma_f32_4(a[2], stat[ch][2], s);
+    s = ptc_mfma_f32_4(a[3], stat[ch][3], s);
   }
   return s;
 }
@@ -409,11 +313,11 @@ nce_fwd_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_t
   constexpr int LDW = 16 * CH + 4;
   const int lane = ptc_lane(), wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
   const int64_t sr = (int64_t)blockIdx.x * NCE_ROWS + wave * 16 + j;
-  nce_f32x4 stat[CH];
+  f32x4 stat[CH];
 #pragma unroll
   for (int ch = 0; ch < CH; ++ch) {
     const int c = 16 * ch + 4 * g;
-    stat[ch] = (sr < P && c < C) ? *reinterpret_cast<const nce_f32x4*>(A + sr * C + c) : nce_splat(0.f);
+    stat[ch] = (sr < P && c < C) ? *reinterpret_cast<const f32x4*>(A + sr * C + c) : nce_splat(0.f);
   }
   const int64_t n_tiles = (P + NCE_TILE - 1) / NCE_TILE;
   const int64_t t_lo = (int64_t)blockIdx.y * tiles_per_split;
@@ -425,7 +329,7 @@ nce_fwd_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_t
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < NCE_TILE / 16; ++t) {
-      const nce_f32x4 s = nce_scores<CH>(img, LDW, t, j, g, stat);
+      const f32x4 s = nce_scores<CH>(img, LDW, t, j, g, stat);
       float z[4], mt = m;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -517,11 +421,11 @@ nce_bwd_kernel(const float* __restrict__ A, const float* __restrict__ B, const f
   const int lane = ptc_lane(), wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
   const int64_t sr = (int64_t)blockIdx.x * NCE_ROWS + wave * 16 + j;
   const float gs = dloss[0] * inv_t / (float)P;
-  nce_f32x4 stat[CH], acc[CH];
+  f32x4 stat[CH], acc[CH];
 #pragma unroll
   for (int ch = 0; ch < CH; ++ch) {
     const int c = 16 * ch + 4 * g;
-    stat[ch] = (sr < P && c < C) ? *reinterpret_cast<const nce_f32x4*>(S_ + sr * C + c) : nce_splat(0.f);
+    stat[ch] = (sr < P && c < C) ? *reinterpret_cast<const f32x4*>(S_ + sr * C + c) : nce_splat(0.f);
     acc[ch] = nce_splat(0.f);
   }
   const float lse_s = (!role_b && sr < P) ? lse[sr] : 0.f;
@@ -536,8 +440,8 @@ nce_bwd_kernel(const float* __restrict__ A, const float* __restrict__ B, const f
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < NCE_TILE / 16; ++t) {
-      const nce_f32x4 s = nce_scores<CH>(img, LDW, t, j, g, stat);
-      nce_f32x4 w;
+      const f32x4 s = nce_scores<CH>(img, LDW, t, j, g, stat);
+      f32x4 w;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t tr = tile * NCE_TILE + 16 * t + 4 * g + r;
@@ -549,10 +453,10 @@ nce_bwd_kernel(const float* __restrict__ A, const float* __restrict__ B, const f
       const float* col = img + (16 * t + 4 * g) * LDW + j;
 #pragma unroll
       for (int ch = 0; ch < CH; ++ch) {
-        acc[ch] = nce_mfma(col[16 * ch], w[0], acc[ch]);
-        acc[ch] = nce_mfma(col[16 * ch + LDW], w[1], acc[ch]);
-        acc[ch] = nce_mfma(col[16 * ch + 2 * LDW], w[2], acc[ch]);
-        acc[ch] = nce_mfma(col[16 * ch + 3 * LDW], w[3], acc[ch]);
+        acc[ch] = ptc_mfma_f32_4(col[16 * ch], w[0], acc[ch]);
+        acc[ch] = ptc_mfma_f32_4(col[16 * ch + LDW], w[1], acc[ch]);
+        acc[ch] = ptc_mfma_f32_4(col[16 * ch + 2 * LDW], w[2], acc[ch]);
+        acc[ch] = ptc_mfma_f32_4(col[16 * ch + 3 * LDW], w[3], acc[ch]);
       }
     }
   }
@@ -560,7 +464,7 @@ nce_bwd_kernel(const float* __restrict__ A, const float* __restrict__ B, const f
 #pragma unroll
     for (int ch = 0; ch < CH; ++ch) {
       const int c = 16 * ch + 4 * g;
-      if (c < C) *reinterpret_cast<nce_f32x4*>(out + sr * C + c) = acc[ch];
+      if (c < C) *reinterpret_cast<f32x4*>(out + sr * C + c) = acc[ch];
     }
   }
 }
@@ -598,9 +502,9 @@ __global__ void nce_segment_add_kernel(const int64_t* __restrict__ skeys, const 
   const int c = (int)(i - p * c4n) * 4;
   const int64_t row = skeys[p];
   if (row >= n_rows || (p > 0 && skeys[p - 1] == row)) return;
-  nce_f32x4 s = nce_splat(0.f);
-  for (int64_t q = p; q < P && skeys[q] == row; ++q) s += *reinterpret_cast<const nce_f32x4*>(dx + order[q] * C + c);
-  *reinterpret_cast<nce_f32x4*>(dfeat + row * C + c) = s;
+  f32x4 s = nce_splat(0.f);
+  for (int64_t q = p; q < P && skeys[q] == row; ++q) s += *reinterpret_cast<const f32x4*>(dx + order[q] * C + c);
+  *reinterpret_cast<f32x4*>(dfeat + row * C + c) = s;
 }
 
 namespace {
@@ -619,18 +523,17 @@ struct NceLayout {
 };
 NceLayout nce_layout(int64_t P, int C) {
   NceLayout Y;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += ptc_align_up(bytes ? bytes : 1, 256); return at; };
+  PtcArena A;
   const int64_t p = P > 0 ? P : 1;
-  Y.part = take((size_t)p * 3 * 4 * NCE_MAX_SPLIT);
-  Y.diag = take((size_t)p * 4);
-  Y.ga = take((size_t)p * C * 4);
-  Y.gb = take((size_t)p * C * 4);
-  Y.keys = take((size_t)p * 8);
-  Y.order = take((size_t)p * 8);
-  Y.skeys = take((size_t)p * 8);
-  Y.scratch = take(ptc_sort_keys_workspace_bytes(p, 1));
-  Y.total = o;
+  Y.part = A.take((size_t)p * 3 * 4 * NCE_MAX_SPLIT);
+  Y.diag = A.take((size_t)p * 4);
+  Y.ga = A.take((size_t)p * C * 4);
+  Y.gb = A.take((size_t)p * C * 4);
+  Y.keys = A.take((size_t)p * 8);
+  Y.order = A.take((size_t)p * 8);
+  Y.skeys = A.take((size_t)p * 8);
+  Y.scratch = A.take(ptc_sort_keys_workspace_bytes(p, 1));
+  Y.total = A.total;
   return Y;
 }
 
@@ -674,28 +577,18 @@ extern "C" int ptc_msc_match(const float* xyz, const int32_t* offset, const floa
   }
   PTC_REQUIRE(xyz && offset, PTC_EINVAL, "ptc_msc_match: null buffer");
   char* ws = (char*)workspace;
-  uint32_t* mm = (uint32_t*)(ws + Y.mm);
-  MscGrid* grid = (MscGrid*)(ws + Y.grid);
-  int64_t* keys = (int64_t*)(ws + Y.keys);
-  int64_t* order = (int64_t*)(ws + Y.order);
-  int64_t* skeys = (int64_t*)(ws + Y.skeys);
-  float4* sxyz = (float4*)(ws + Y.sxyz);
-  PTC_HIP(hipMemsetAsync(mm, 0xff, 12, s));
-  PTC_HIP(hipMemsetAsync(mm + 3, 0, 12, s));
-  int gb = msc_grid1(n);
-  gb = gb > 1024 ? 1024 : gb;
-  hipLaunchKernelGGL(msc_bounds_kernel, dim3(gb), dim3(MSC_THREADS), 0, s, xyz, n, mm);
-  PTC_CHECK_LAUNCH("msc_bounds_kernel");
-  hipLaunchKernelGGL(msc_grid_params_kernel, dim3(1), dim3(64), 0, s, mm, (double)max_radius, grid, stats);
-  PTC_CHECK_LAUNCH("msc_grid_params_kernel");
-  hipLaunchKernelGGL(msc_keys_kernel, dim3(msc_grid1(n)), dim3(MSC_THREADS), 0, s, xyz, offset, b, n, grid, keys);
+  PtcCellGrid* grid = (PtcCellGrid*)(ws + Y.g.grid);
+  int64_t* keys = (int64_t*)(ws + Y.g.keys);
+  int64_t* skeys = (int64_t*)(ws + Y.g.skeys);
+  float4* sxyz = (float4*)(ws + Y.g.sxyz);
+  int rc = ptc_cell_grid_params(xyz, n, (double)max_radius, (uint32_t*)(ws + Y.g.mm), grid, stream);
+  if (rc != PTC_OK) return rc;
+  hipLaunchKernelGGL(msc_keys_kernel, dim3(msc_grid1(n)), dim3(MSC_THREADS), 0, s, xyz, offset, b, n, grid, keys, stats);
   PTC_CHECK_LAUNCH("msc_keys_kernel");
   int scene_bits = 1;
   while ((1 << scene_bits) <= b) ++scene_bits;
-  int rc = ptc_sort_keys_ex(keys, n, 1, 0, 48 + scene_bits, order, nullptr, skeys, ws + Y.scratch, Y.total - Y.scratch, stream);
+  rc = ptc_cell_grid_sort(xyz, keys, n, 48 + scene_bits, (int64_t*)(ws + Y.g.order), skeys, sxyz, ws + Y.g.scratch, Y.g.scratch_bytes, stream);
   if (rc != PTC_OK) return rc;
-  hipLaunchKernelGGL(msc_sorted_kernel, dim3(msc_grid1(n)), dim3(MSC_THREADS), 0, s, xyz, order, n, sxyz);
-  PTC_CHECK_LAUNCH("msc_sorted_kernel");
   hipLaunchKernelGGL(msc_match_kernel, dim3(msc_grid1(m)), dim3(MSC_THREADS), 0, s, new_xyz, new_offset, b, m, grid, skeys, sxyz, n, k,
                      max_radius, count, cand, stats);
   PTC_CHECK_LAUNCH("msc_match_kernel");

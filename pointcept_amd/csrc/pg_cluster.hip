@@ -4,8 +4,8 @@
 // 1  Ball query.  Point k is a neighbour of query i iff both carry the same batch index and the fp32 expression
 //    d2 = (ox-x)*(ox-x) + (oy-y)*(oy-y) + (oz-z)*(oz-z) (unfused, in that order) is < radius*radius; the list holds the first 1000
 //    neighbours in ascending index order (the reference breaks at the 1001st).  A uniform grid of cells of edge >= |radius| (grown when
-//    the extent would overflow the 16-bit cell fields of the packed key) is sorted with ptc_sort_keys, so each cell's points are
-//    ascending by index.  The count pass counts hits over the 27 neighbour cells and stops at the 1001st (len = min(count, 1000)); an
+//    the extent would overflow the 16-bit cell fields of the packed key; cell_grid.h) is sorted with ptc_sort_keys, so each cell's points
+//    are ascending by index.  The count pass counts hits over the 27 neighbour cells and stops at the 1001st (len = min(count, 1000)); an
 //    exclusive scan gives exact starts, then the fill pass merges the 27 ascending cell lists and stops after `len` hits.  No per-thread
 //    list buffer, no retry, no float atomics.  A point with a non-finite coordinate has no neighbour, not even itself.
 // 2  Clustering.  Edges i->j for j in list(i) with label[j] == label[i].  Undirected components by a lock-free integer union-find
@@ -19,141 +19,52 @@
 // 3  Proposal scores: per cluster the member count, the class label[seed] and the mean of softmax(logits)[member, class], one
 //    workgroup per cluster with a fixed-order reduction.  Dense [P, N] int32 proposal masks.
 // 4  Bias losses (masked L1 + negative cosine) forward as two fixed-order reduction levels, and their backward in one pass.
-#include "ptc_common.h"
+#include "cell_grid.h"
 
 #define PG_MAX_NBR 1000
 #define PG_THREADS 256
-#define PG_CELL_MAX 65533           // cell fields hold 0..65535; neighbours reach -1..65534
-#define PG_EXTENT_CELLS 60000.0
-#define PG_EDGE_MARGIN 1.0001       // cell edge >= |radius| * (1 + 1e-4): fp32 rounding of d2 never reaches past one cell
 #define PG_SENTINEL 0x7fffffffffffffffll
 
 namespace {
 
-__device__ __forceinline__ uint32_t pg_enc(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float pg_dec(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-__device__ __forceinline__ bool pg_finite3(float x, float y, float z) {
-  return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
-
 // the reference's expression, kept unfused
 __device__ __forceinline__ bool pg_hit(float ox, float oy, float oz, float x, float y, float z, float r2) {
-#pragma clang fp contract(off)
-  const float dx = ox - x, dy = oy - y, dz = oz - z;
-  const float d2 = dx * dx + dy * dy + dz * dz;
-  return d2 < r2;
+  return ptc_dist2(ox, oy, oz, x, y, z) < r2;
 }
-
-struct PgGrid {          // written by pg_grid_params_kernel
-  double mn[3];
-  double edge;
-};
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // 1. ball query
 // ---------------------------------------------------------------------------------------------------------------------------------
-__global__ void pg_bounds_kernel(const float* __restrict__ xyz, int64_t n, uint32_t* __restrict__ mm) {
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
-    if (!pg_finite3(x, y, z)) continue;
-    const uint32_t e[3] = {pg_enc(x), pg_enc(y), pg_enc(z)};
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = e[a] < lo[a] ? e[a] : lo[a];
-      hi[a] = e[a] > hi[a] ? e[a] : hi[a];
-    }
-  }
-  for (int a = 0; a < 3; ++a) {
-    if (hi[a] == 0u) continue;        // this thread saw no finite point
-    atomicMin(mm + a, lo[a]);
-    atomicMax(mm + 3 + a, hi[a]);
-  }
-}
-
-__global__ void pg_grid_params_kernel(const uint32_t* __restrict__ mm, double rabs, PgGrid* __restrict__ g) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double ext = 0.0;
-  const bool any = mm[3] != 0u;
-  for (int a = 0; a < 3; ++a) {
-    const double lo = any ? (double)pg_dec(mm[a]) : 0.0, hi = any ? (double)pg_dec(mm[3 + a]) : 0.0;
-    g->mn[a] = lo;
-    ext = hi - lo > ext ? hi - lo : ext;
-  }
-  double edge = rabs * PG_EDGE_MARGIN;
-  if (ext / edge > PG_EXTENT_CELLS) edge = ext / PG_EXTENT_CELLS;
-  g->edge = edge;
-}
-
-__device__ __forceinline__ int pg_cell(float v, double mn, double edge) {
-  double c = floor(((double)v - mn) / edge);
-  c = c < 0.0 ? 0.0 : (c > (double)PG_CELL_MAX ? (double)PG_CELL_MAX : c);
-  return (int)c;
-}
-
-__device__ __forceinline__ int64_t pg_key(int b, int cx, int cy, int cz) {
-  return ((int64_t)b << 48) | ((int64_t)cz << 32) | ((int64_t)cy << 16) | (int64_t)cx;
-}
-
 __global__ void pg_keys_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ bidx, int64_t n, int n_batch,
-                               const PgGrid* __restrict__ g, int64_t* __restrict__ keys) {
+                               const PtcCellGrid* __restrict__ g, int64_t* __restrict__ keys) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
   const int b = bidx[i];
-  if (!pg_finite3(x, y, z) || b < 0 || b >= n_batch) {
+  if (!ptc_finite3(x, y, z) || b < 0 || b >= n_batch) {
     keys[i] = PG_SENTINEL;
     return;
   }
   const double e = g->edge;
-  keys[i] = pg_key(b, pg_cell(x, g->mn[0], e), pg_cell(y, g->mn[1], e), pg_cell(z, g->mn[2], e));
-}
-
-// sorted copies: skeys[p] = keys[order[p]], sxyz[p] = (xyz[order[p]], bits of order[p])
-__global__ void pg_sorted_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ keys, const int64_t* __restrict__ order,
-                                 int64_t n, int64_t* __restrict__ skeys, float4* __restrict__ sxyz) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  const int64_t k = order[p];
-  skeys[p] = keys[k];
-  sxyz[p] = make_float4(xyz[k * 3], xyz[k * 3 + 1], xyz[k * 3 + 2], __int_as_float((int)k));
-}
-
-__device__ __forceinline__ int64_t pg_lower_bound(const int64_t* __restrict__ a, int64_t lo, int64_t hi, int64_t key) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
+  keys[i] = ptc_cell_key(b, ptc_cell(x, g->mn[0], e), ptc_cell(y, g->mn[1], e), ptc_cell(z, g->mn[2], e));
 }
 
 // the up to 27 non-empty sorted ranges [beg, end) of the cells around query i; returns their number
 __device__ __forceinline__ int pg_ranges(const int64_t* __restrict__ skeys, int64_t n, int64_t key, int (&beg)[27], int (&end)[27]) {
   const int b = (int)(key >> 48), cz = (int)((key >> 32) & 0xffff), cy = (int)((key >> 16) & 0xffff), cx = (int)(key & 0xffff);
   int nl = 0;
-  for (int dz = -1; dz <= 1; ++dz) {
-    if (cz + dz < 0) continue;
-    for (int dy = -1; dy <= 1; ++dy) {
-      if (cy + dy < 0) continue;
-      const int x0 = cx > 0 ? cx - 1 : 0;
-      const int64_t lo = pg_lower_bound(skeys, 0, n, pg_key(b, x0, cy + dy, cz + dz));
-      const int64_t hi = pg_lower_bound(skeys, lo, n, pg_key(b, cx + 2, cy + dy, cz + dz));
-      int64_t s = lo;
-      for (int x = x0; x <= cx + 1; ++x) {
-        const int64_t e = x == cx + 1 ? hi : pg_lower_bound(skeys, s, hi, pg_key(b, x + 1, cy + dy, cz + dz));
-        if (e > s) {
-          beg[nl] = (int)s;
-          end[nl] = (int)e;
-          ++nl;
-        }
-        s = e;
+  ptc_cell_runs(skeys, n, b, cx, cy, cz, [&](int64_t lo, int64_t hi, int y, int z) {      // each run split into its cells
+    int64_t s = lo;
+    for (int x = cx > 0 ? cx - 1 : 0; x <= cx + 1; ++x) {
+      const int64_t e = x == cx + 1 ? hi : ptc_lower_bound(skeys, s, hi, ptc_cell_key(b, x + 1, y, z));
+      if (e > s) {
+        beg[nl] = (int)s;
+        end[nl] = (int)e;
+        ++nl;
       }
+      s = e;
     }
-  }
+  });
   return nl;
 }
 
@@ -219,26 +130,20 @@ __global__ void __launch_bounds__(PG_THREADS) pg_fill_kernel(const float* __rest
 }
 
 struct BqLayout {
-  size_t mm, grid, keys, order, skeys, sxyz, len, trunc, start, scratch, total;
+  PtcCellGridLayout g;
+  size_t len, trunc, start, total;
 };
 
 BqLayout bq_layout(int64_t n) {
   BqLayout Y;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += ptc_align_up(bytes ? bytes : 1, 256); return at; };
+  PtcArena A;
   const int64_t m = n > 0 ? n : 1;
-  Y.mm = take(6 * 4);
-  Y.grid = take(sizeof(PgGrid));
-  Y.keys = take((size_t)m * 8);
-  Y.order = take((size_t)m * 8);
-  Y.skeys = take((size_t)m * 8);
-  Y.sxyz = take((size_t)m * 16);
-  Y.len = take((size_t)m * 4);
-  Y.trunc = take((size_t)m * 4);
-  Y.start = take((size_t)m * 8);
-  size_t s1 = ptc_sort_keys_workspace_bytes(m, 1), s2 = ptc_exclusive_scan_workspace_bytes(m);
-  Y.scratch = take(s1 > s2 ? s1 : s2);
-  Y.total = o;
+  Y.g.take_arrays(A, m);
+  Y.len = A.take((size_t)m * 4);
+  Y.trunc = A.take((size_t)m * 4);
+  Y.start = A.take((size_t)m * 8);
+  Y.g.take_scratch(A, m, ptc_exclusive_scan_workspace_bytes(m));      // the scan of the lengths runs in it too
+  Y.total = A.total;
   return Y;
 }
 
@@ -451,32 +356,29 @@ struct ClLayout {
 
 ClLayout cl_layout(int64_t n) {
   ClLayout Y;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += ptc_align_up(bytes ? bytes : 1, 256); return at; };
+  PtcArena A;
   const int64_t m = n > 0 ? n : 1;
-  // flags .. excount are contiguous, zeroed by the init kernel
-  Y.parent = take((size_t)m * 4);
-  Y.flags = o; o += (size_t)m * 4;
-  Y.compflag = o; o += (size_t)m * 4;
-  Y.visited = o; o += (size_t)m * 4;
-  Y.size = o; o += (size_t)m * 4;
-  Y.excount = o; o += 4;
-  o = ptc_align_up(o, 256);
-  Y.sub = take((size_t)m * 4);
-  Y.keep = take((size_t)m * 4);
-  Y.ksize = take((size_t)m * 4);
-  Y.cstart = take((size_t)m * 4);
-  Y.cend = take((size_t)m * 4);
-  Y.exlist = take((size_t)m * 4);
-  Y.fa = take((size_t)m * 4);
-  Y.fb = take((size_t)m * 4);
-  Y.cid = take((size_t)m * 8);
-  Y.koff = take((size_t)m * 8);
-  Y.keys = take((size_t)m * 8);
-  Y.order = take((size_t)m * 8);
+  Y.parent = A.take((size_t)m * 4);
+  Y.flags = A.take((size_t)m * 16 + 4);      // flags .. excount are one piece, zeroed by the init kernel
+  Y.compflag = Y.flags + (size_t)m * 4;
+  Y.visited = Y.compflag + (size_t)m * 4;
+  Y.size = Y.visited + (size_t)m * 4;
+  Y.excount = Y.size + (size_t)m * 4;
+  Y.sub = A.take((size_t)m * 4);
+  Y.keep = A.take((size_t)m * 4);
+  Y.ksize = A.take((size_t)m * 4);
+  Y.cstart = A.take((size_t)m * 4);
+  Y.cend = A.take((size_t)m * 4);
+  Y.exlist = A.take((size_t)m * 4);
+  Y.fa = A.take((size_t)m * 4);
+  Y.fb = A.take((size_t)m * 4);
+  Y.cid = A.take((size_t)m * 8);
+  Y.koff = A.take((size_t)m * 8);
+  Y.keys = A.take((size_t)m * 8);
+  Y.order = A.take((size_t)m * 8);
   size_t s1 = ptc_sort_keys_workspace_bytes(m, 1), s2 = ptc_exclusive_scan_workspace_bytes(m);
-  Y.scratch = take(s1 > s2 ? s1 : s2);
-  Y.total = o;
+  Y.scratch = A.take(s1 > s2 ? s1 : s2);
+  Y.total = A.total;
   return Y;
 }
 
@@ -672,35 +574,25 @@ extern "C" int ptc_pg_ball_query_count(const float* xyz, const int32_t* batch_id
     PTC_HIP(hipMemsetAsync(start_len, 0, (size_t)n * 8, s));
     return PTC_OK;
   }
-  uint32_t* mm = (uint32_t*)(ws + Y.mm);
-  PTC_HIP(hipMemsetAsync(mm, 0xff, 12, s));
-  PTC_HIP(hipMemsetAsync(mm + 3, 0, 12, s));
+  PtcCellGrid* grid = (PtcCellGrid*)(ws + Y.g.grid);
+  int rc = ptc_cell_grid_params(xyz, n, (double)rabs, (uint32_t*)(ws + Y.g.mm), grid, stream);
+  if (rc != PTC_OK) return rc;
   const int g1 = pg_grid1(n);
-  hipLaunchKernelGGL(pg_bounds_kernel, dim3((unsigned)(g1 > 1024 ? 1024 : g1)), dim3(PG_THREADS), 0, s, xyz, n, mm);
-  PTC_CHECK_LAUNCH("pg_bounds_kernel");
-  PgGrid* grid = (PgGrid*)(ws + Y.grid);
-  hipLaunchKernelGGL(pg_grid_params_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)mm, (double)rabs, grid);
-  PTC_CHECK_LAUNCH("pg_grid_params_kernel");
-  int64_t* keys = (int64_t*)(ws + Y.keys);
-  int64_t* order = (int64_t*)(ws + Y.order);
-  int64_t* skeys = (int64_t*)(ws + Y.skeys);
-  float4* sxyz = (float4*)(ws + Y.sxyz);
+  int64_t* keys = (int64_t*)(ws + Y.g.keys);
+  int64_t* skeys = (int64_t*)(ws + Y.g.skeys);
+  float4* sxyz = (float4*)(ws + Y.g.sxyz);
   int32_t* len = (int32_t*)(ws + Y.len);
   int32_t* trunc = (int32_t*)(ws + Y.trunc);
   int64_t* start = (int64_t*)(ws + Y.start);
-  hipLaunchKernelGGL(pg_keys_kernel, dim3((unsigned)g1), dim3(PG_THREADS), 0, s, xyz, batch_idxs, n, n_batch, (const PgGrid*)grid, keys);
+  hipLaunchKernelGGL(pg_keys_kernel, dim3((unsigned)g1), dim3(PG_THREADS), 0, s, xyz, batch_idxs, n, n_batch, (const PtcCellGrid*)grid, keys);
   PTC_CHECK_LAUNCH("pg_keys_kernel");
-  const size_t sws = ptc_sort_keys_workspace_bytes(n, 1);
-  int rc = ptc_sort_keys(keys, n, 1, 0, 63, order, nullptr, ws + Y.scratch, sws, stream);
+  rc = ptc_cell_grid_sort(xyz, keys, n, 63, (int64_t*)(ws + Y.g.order), skeys, sxyz, ws + Y.g.scratch, Y.g.scratch_bytes, stream);
   if (rc != PTC_OK) return rc;
-  hipLaunchKernelGGL(pg_sorted_kernel, dim3((unsigned)g1), dim3(PG_THREADS), 0, s, xyz, (const int64_t*)keys, (const int64_t*)order, n,
-                     skeys, sxyz);
-  PTC_CHECK_LAUNCH("pg_sorted_kernel");
   const float r2 = radius * radius;
   hipLaunchKernelGGL(pg_count_kernel, dim3((unsigned)g1), dim3(PG_THREADS), 0, s, xyz, (const int64_t*)keys, (const int64_t*)skeys,
                      (const float4*)sxyz, n, r2, len, trunc);
   PTC_CHECK_LAUNCH("pg_count_kernel");
-  rc = ptc_exclusive_scan_i32(len, n, start, ws + Y.scratch, ptc_exclusive_scan_workspace_bytes(n), stream);
+  rc = ptc_exclusive_scan_i32(len, n, start, ws + Y.g.scratch, ptc_exclusive_scan_workspace_bytes(n), stream);
   if (rc != PTC_OK) return rc;
   hipLaunchKernelGGL(pg_start_len_kernel, dim3((unsigned)g1), dim3(PG_THREADS), 0, s, (const int32_t*)len, (const int32_t*)trunc,
                      (const int64_t*)start, n, start_len, total);
@@ -717,7 +609,7 @@ extern "C" int ptc_pg_ball_query_fill(const float* xyz, int64_t n, float radius,
   PTC_REQUIRE(xyz && start_len && idx, PTC_EINVAL, "ptc_pg_ball_query_fill: null buffer");
   char* ws = (char*)workspace;
   hipLaunchKernelGGL(pg_fill_kernel, dim3((unsigned)pg_grid1(n)), dim3(PG_THREADS), 0, (hipStream_t)stream, xyz,
-                     (const int64_t*)(ws + Y.keys), (const int64_t*)(ws + Y.skeys), (const float4*)(ws + Y.sxyz), n, radius * radius,
+                     (const int64_t*)(ws + Y.g.keys), (const int64_t*)(ws + Y.g.skeys), (const float4*)(ws + Y.g.sxyz), n, radius * radius,
                      start_len, idx);
   PTC_CHECK_LAUNCH("pg_fill_kernel");
   return PTC_OK;

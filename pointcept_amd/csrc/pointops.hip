@@ -19,13 +19,6 @@
 #define KNN_THREADS 256
 #define KNN_TILE 1024
 
-__device__ __forceinline__ float po_dist2(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)      // HIP's __fmul_rn / __fadd_rn are plain operators: without this they fuse into FMAs
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-  return (xx + yy) + zz;
-}
-
 // smallest i with p < ends[i] (ends ascending, p < ends[b-1])
 __device__ __forceinline__ int po_scene_of(const int* __restrict__ ends, int b, int64_t p) {
   int lo = 0, hi = b - 1;
@@ -76,7 +69,7 @@ knn_query_kernel(const float* __restrict__ xyz, const int* __restrict__ offset, 
     const int i0 = (start > t0 ? start : t0) - t0;
     const int i1 = ((end < t0 + cnt ? end : t0 + cnt)) - t0;
     for (int e = i0; e < i1; ++e) {
-      const float d2 = po_dist2(qx, qy, qz, sx[e], sy[e], sz[e]);
+      const float d2 = ptc_dist2(qx, qy, qz, sx[e], sy[e], sz[e]);
       if (d2 < bd[K - 1]) {
         int pos = 0;                                  // insert after every entry <= d2: ascending (distance, index)
 #pragma unroll
@@ -144,7 +137,7 @@ fps_kernel(const float* __restrict__ xyz, const int* __restrict__ offset, const 
     float best = -1.f;
     int arg = start_n;
     for (int k = start_n + tid; k < end_n; k += FPS_THREADS) {
-      const float d = po_dist2(xyz[3 * (int64_t)k], xyz[3 * (int64_t)k + 1], xyz[3 * (int64_t)k + 2], x1, y1, z1);
+      const float d = ptc_dist2(xyz[3 * (int64_t)k], xyz[3 * (int64_t)k + 1], xyz[3 * (int64_t)k + 2], x1, y1, z1);
       const float t = fminf(d, tmp[k]);
       tmp[k] = t;
       if (t > best) { best = t; arg = k; }            // ascending k: the lowest index among equals stays
@@ -225,7 +218,7 @@ ball_query_kernel(const float* __restrict__ xyz, const int* __restrict__ offset,
     float d = 0.f;
     bool in = false;
     if (p < end) {
-      d = po_dist2(qx, qy, qz, xyz[3 * (int64_t)p], xyz[3 * (int64_t)p + 1], xyz[3 * (int64_t)p + 2]);
+      d = ptc_dist2(qx, qy, qz, xyz[3 * (int64_t)p], xyz[3 * (int64_t)p + 1], xyz[3 * (int64_t)p + 2]);
       in = d <= 1e-5f || (d >= min_r2 && d < max_r2);
     }
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(in);
@@ -301,7 +294,7 @@ random_ball_query_kernel(const float* __restrict__ xyz, const int* __restrict__ 
     bool in = false;
     if (i < end) {
       p = order[i];
-      d = po_dist2(qx, qy, qz, xyz[3 * (int64_t)p], xyz[3 * (int64_t)p + 1], xyz[3 * (int64_t)p + 2]);
+      d = ptc_dist2(qx, qy, qz, xyz[3 * (int64_t)p], xyz[3 * (int64_t)p + 1], xyz[3 * (int64_t)p + 2]);
       in = d <= 1e-5f || (d >= min_r2 && d < max_r2);
     }
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(in);

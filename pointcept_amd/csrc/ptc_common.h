@@ -41,6 +41,20 @@ void ptc_set_error(const char* fmt, ...);
 static inline int64_t ptc_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t ptc_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Carves a workspace into 256-byte aligned pieces: take() returns the piece's offset (an empty request still takes one slot, so no
+// two pieces share an address), take_as<T>() the pointer into `base`; `total` is the size so far.
+struct PtcArena {
+  char* base;
+  size_t total = 0;
+  explicit PtcArena(void* b = nullptr) : base((char*)b) {}
+  size_t take(size_t bytes) {
+    const size_t at = total;
+    total += ptc_align_up(bytes ? bytes : 1, 256);
+    return at;
+  }
+  template <typename T> T* take_as(size_t bytes) { return (T*)(base + take(bytes)); }
+};
+
 // ---- storage types --------------------------------------------------------------------------
 // bf16 / f16 are carried as raw 16-bit patterns; arithmetic is always fp32.
 struct bf16_t { uint16_t x; };
@@ -86,6 +100,23 @@ static inline size_t ptc_dtype_size(int dtype) { return dtype == PTC_F32 ? 4 : 2
 
 // ---- wave helpers ---------------------------------------------------------------------------
 __device__ __forceinline__ int ptc_lane() { return threadIdx.x & 63; }
+
+// ---- small device helpers shared by the point-cloud operators ----------------------------------------------------------------------
+// order-preserving map float -> uint32 (unsigned compare = float compare; 0 is below every encoded value) and its inverse
+__device__ __forceinline__ uint32_t ptc_float_enc(float f) {
+  const uint32_t b = __float_as_uint(f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ptc_float_dec(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// squared distance ((dx*dx + dy*dy) + dz*dz) in fp32 with every operation rounded, the reference's expression: the CPU oracles
+// reproduce it bit for bit
+__device__ __forceinline__ float ptc_dist2(float ax, float ay, float az, float bx, float by, float bz) {
+#pragma clang fp contract(off)      // HIP's __fmul_rn / __fadd_rn are plain operators: without this they fuse into FMAs
+  const float dx = ax - bx, dy = ay - by, dz = az - bz;
+  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  return (xx + yy) + zz;
+}
 
 // f(ptc_int<0>{}), f(ptc_int<1>{}), ...: an unrolled loop whose index is a TYPE (a register array indexed by it never turns into a
 // runtime-indexed -- i.e. scratch -- access, whatever the control flow inside f)
@@ -161,3 +192,10 @@ __device__ __forceinline__ float ptc_gelu_grad(float z) {       // Phi(z) + z ph
 // ptc_sort_keys (scan_sort.hip) that also returns the key words in sorted order; see there.
 int ptc_sort_keys_ex(const int64_t* keys, int64_t n, int k, int begin_bit, int end_bit, int64_t* order, int64_t* inverse,
                      int64_t* sorted_keys, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+// The uniform cell grid of cell_grid.h, built in two steps around the caller's own keys kernel (cell_grid.hip):
+// 1. bounds of the finite rows of xyz [n, 3] -> grid origin and cell edge (>= radius, radius > 0); `mm` = 6 scratch words
+struct PtcCellGrid;
+int ptc_cell_grid_params(const float* xyz, int64_t n, double radius, uint32_t* mm, PtcCellGrid* grid, ptc_stream_t stream);
+// 2. stable sort of the keys over bits [0, end_bit) -> order, sorted keys and sxyz[p] = (xyz[order[p]], bits of order[p])
+int ptc_cell_grid_sort(const float* xyz, const int64_t* keys, int64_t n, int end_bit, int64_t* order, int64_t* sorted_keys, float4* sxyz,
+                       void* scratch, size_t scratch_bytes, ptc_stream_t stream);
