@@ -525,6 +525,26 @@ int ptc_lovasz_softmax(const void* logits, int64_t row_stride, const int64_t* ta
                        int64_t ignore_index, float* loss, float* dlogits, void* workspace, size_t workspace_bytes,
                        ptc_stream_t stream);
 
+/* The same loss for 1 <= c <= 1024 classes (ScanNet200: 200, ScanNet++: 100) over the classes PRESENT only: the reference sorts
+ * the classes `labels.unique()` returns (lovasz.py:129-134); a class without a counted label has zero loss and zero
+ * probability gradient, so its row of the error matrix is never built.
+ * ptc_lovasz_present: class_count [c] = counted labels per class (a label is not counted if it equals ignore_index, is negative
+ *   or >= c); the P present classes ranked in ascending class order: row_of [c] = compact row of a class (-1 = absent),
+ *   class_of [c] = class of a row (the first P entries; -1 after them), n_present [1] = P.  All int32, DEVICE, on `stream`.
+ * ptc_lovasz_softmax_rows: loss and dlogits as ptc_lovasz_softmax, from those four arrays; `rows` = the HOST's copy of P
+ *   (it sizes the workspace and the grids; the kernels never use more rows than it).  rows == 0 or n == 0: loss 0, dlogits 0.
+ *   c > 1024: PTC_EUNSUPPORTED.  Workspace: keys 8 + order 8 + flags 4 + scan 8 + gprob 4 bytes per (row, point) slot plus
+ *   the radix sort's ping-pong buffers (24 bytes per slot + histograms) = ~56 * rows * n bytes (9.2 GB at 819200 x 200 with
+ *   every class present, 2.8 GB with 60); 0 when rows == 0 or n == 0.  Integer atomics only, reductions in a fixed order:
+ *   bit-reproducible.  Differs from ptc_lovasz_softmax in the summation order of the softmax denominator and of <g, p>. */
+int ptc_lovasz_present(const int64_t* target, int64_t n, int c, int64_t ignore_index, int32_t* class_count, int32_t* row_of,
+                       int32_t* class_of, int32_t* n_present, ptc_stream_t stream);
+size_t ptc_lovasz_softmax_rows_workspace_bytes(int64_t n, int c, int rows);
+int ptc_lovasz_softmax_rows(const void* logits, int64_t row_stride, const int64_t* target, int64_t n, int c, int dtype,
+                            int64_t ignore_index, const int32_t* class_count, const int32_t* row_of, const int32_t* class_of,
+                            const int32_t* n_present, int rows, float* loss, float* dlogits, void* workspace,
+                            size_t workspace_bytes, ptc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * K. Voxelisation front end (GridSample), for point clouds that already live on the device.
  * Replaces the numpy prologue of GridSample.__call__, pointcept/datasets/transform.py:867-875 with

@@ -184,6 +184,10 @@ _SIGNATURES = {
     "ptc_cac_distill_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "ptc_lovasz_softmax_workspace_bytes": (c_size, [c_i64, c_int]),
     "ptc_lovasz_softmax": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_lovasz_present": (c_int, [c_ptr, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "ptc_lovasz_softmax_rows_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
+    "ptc_lovasz_softmax_rows": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
+                                        c_ptr, c_size, c_ptr]),
 }
 
 PTC_F32, PTC_F16, PTC_BF16 = 0, 1, 2

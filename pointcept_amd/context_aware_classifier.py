@@ -12,7 +12,9 @@ compat.register_models(MODELS, names=["CAC-v1m1"]).
   adaptive branch, as in the reference -- running_mean / running_var / num_batches_tracked (B + 1 after one forward) follow it; the
   scene boundaries are the forward's one host read.  In eval mode the projection runs on the whole batch at once.
 * Linear and BatchNorm1d are the engine's; the criteria (CrossEntropyLoss, LovaszLoss with loss_weight / ignore_index) map onto
-  functional.cross_entropy / lovasz_softmax; an already built callable is taken as is; any other criterion type is refused by name.
+  functional.cross_entropy / lovasz_softmax (both up to 1024 classes; above 64 the Lovasz kernels sort the classes present only: ~56 B x
+  present classes x points of workspace, one host read of their number per call); an already built callable is taken as is; any other
+  criterion type is refused by name.
 * Autocast: the kernels take fp32.  Under autocast their inputs are cast with .float() (functional.cac_*), the Linear layers follow
   autocast as everywhere in the engine.
 * PTC_CAC=0 (config.CAC_KERNELS), CPU tensors, and shapes the kernels refuse (K outside 2..256, C not a multiple of 16 up to 128)

@@ -788,8 +788,12 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int 
 
 class _LovaszSoftmax(Function):
     @staticmethod
-    def forward(ctx, logits, target, ignore_index):
-        loss, dlogits = ops.lovasz_softmax(logits, target, ignore_index)
+    def forward(ctx, logits, target, ignore_index, present=None):
+        # the handle is passed on only when one was given: a three-argument backend (the oracle stand-in) keeps serving the call
+        if present is None:
+            loss, dlogits = ops.lovasz_softmax(logits, target, ignore_index)
+        else:
+            loss, dlogits = ops.lovasz_softmax(logits, target, ignore_index, present=present)
         ctx.save_for_backward(dlogits)
         ctx.dtype = logits.dtype
         return loss
@@ -798,16 +802,26 @@ class _LovaszSoftmax(Function):
     @once_differentiable
     def backward(ctx, g):
         (dlogits,) = ctx.saved_tensors
-        return (dlogits * g.float()).to(ctx.dtype), None, None
+        return (dlogits * g.float()).to(ctx.dtype), None, None, None
 
 
-def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -1) -> torch.Tensor:
-    """LovaszLoss(mode="multiclass", ignore_index=ignore_index) on seg logits [N, C]
-    (pointcept/models/losses/lovasz.py:209-260; second criterion of scannet/semseg-pt-v3m1-0-base.py:49-52):
-    softmax, per-class errors, ONE segmented sort, exact Jaccard steps and the gradient, all on device."""
+def lovasz_present(target: torch.Tensor, num_classes: int, ignore_index: int = -1):
+    """The ranked list of the classes present in `target`, made ahead of lovasz_softmax(..., present=handle) (ops.lovasz_present):
+    asked for before the backbone runs, the one number the host needs (P) has arrived by the time the loss is called."""
+    return ops.lovasz_present(target, int(num_classes), int(ignore_index))
+
+
+def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -1, present=None) -> torch.Tensor:
+    """LovaszLoss(mode="multiclass", ignore_index=ignore_index) on seg logits [N, C], C <= 1024
+    (pointcept/models/losses/lovasz.py:209-260; second criterion of scannet/semseg-pt-v3m1-0-base.py:49-52 and of
+    scannet200/semseg-pt-v3m1-0-base.py): softmax, per-class errors, ONE segmented sort, exact Jaccard steps and the gradient, all on
+    device.  More than 64 classes, or any width with `present` (lovasz_present of the same target): only the classes present are
+    sorted; without a handle that path reads their number back once (one host synchronisation)."""
     if logits.dim() != 2:
         raise PtcoreError("lovasz_softmax expects [N, C] logits")
-    return _LovaszSoftmax.apply(logits, target, int(ignore_index))
+    if present is None:
+        return _LovaszSoftmax.apply(logits, target, int(ignore_index))
+    return _LovaszSoftmax.apply(logits, target, int(ignore_index), present)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1085,22 +1085,113 @@ def cross_entropy_bwd(logits: torch.Tensor, target: torch.Tensor, lse: torch.Ten
     return out
 
 
-def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, ignore_index: int):
+LOVASZ_DENSE_MAX_C = 64         # csrc/lovasz.hip LV_MAX_C: the dense [C, N] path
+LOVASZ_MAX_C = 1024             # LW_MAX_C: the row-compacted path
+
+
+class LovaszPresent:
+    """What ptc_lovasz_present leaves on the device for one (target, num_classes, ignore_index): class_count / row_of / class_of [C]
+    and n_present [1] (int32), the copy of n_present on its way into pinned host memory, and the identity of `target` (data pointer,
+    shape, version counter) the handle is valid for."""
+
+    __slots__ = ("class_count", "row_of", "class_of", "n_present", "num_classes", "ignore_index", "_host", "_event", "_target", "_ident")
+
+    def __init__(self, target, num_classes, ignore_index, class_count, row_of, class_of, n_present, host, event):
+        self.class_count, self.row_of, self.class_of, self.n_present = class_count, row_of, class_of, n_present
+        self.num_classes, self.ignore_index = int(num_classes), int(ignore_index)
+        self._host, self._event = host, event
+        self._target = target                      # kept alive: its storage cannot be handed to another tensor meanwhile
+        self._ident = _target_ident(target)
+
+    def rows(self) -> int:
+        """P on the host; waits for the copy only if it has not landed yet"""
+        if self._event is not None:
+            self._event.synchronize()
+            self._event = None
+        return int(self._host[0])
+
+    def matches(self, target, num_classes, ignore_index) -> bool:
+        return (self._ident == _target_ident(target) and self.num_classes == int(num_classes) and self.ignore_index == int(ignore_index))
+
+
+def _target_ident(target):
+    return (target.data_ptr(), tuple(target.shape), tuple(target.stride()), target._version, target.device)
+
+
+def lovasz_present(target: torch.Tensor, num_classes: int, ignore_index: int) -> LovaszPresent:
+    """The classes with at least one counted label, ranked, for lovasz_softmax(..., present=handle): everything stays on the device
+    and on the current stream; P travels to pinned host memory behind an event, so a caller that asks early (the segmentor: before
+    the backbone) finds it there when the loss needs it."""
+    require_cuda(target)
+    if target.dtype != torch.int64 or target.dim() != 1:
+        raise PtcoreError("target must be int64 [N]")
+    c = int(num_classes)
+    if not 1 <= c <= LOVASZ_MAX_C:
+        raise PtcoreError(f"lovasz_present: {c} classes (1 .. {LOVASZ_MAX_C} are served)")
+    tg = target.contiguous()
+    buf = torch.empty(3 * c + 1, dtype=torch.int32, device=tg.device)
+    count, row_of, class_of, n_present = buf[:c], buf[c:2 * c], buf[2 * c:3 * c], buf[3 * c:]
+    check(lib().ptc_lovasz_present(ptr(tg), tg.shape[0], c, int(ignore_index), ptr(count), ptr(row_of), ptr(class_of), ptr(n_present),
+                                   stream_ptr()), "ptc_lovasz_present")
+    if tg.is_cuda:
+        host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        host.copy_(n_present, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+    else:
+        host, event = n_present, None
+    return LovaszPresent(target, c, ignore_index, count, row_of, class_of, n_present, host, event)
+
+
+def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, ignore_index: int, present: Optional[LovaszPresent] = None):
     """Lovasz-Softmax (multiclass, classes present, whole batch: pointcept/models/losses/lovasz.py:118-146) ->
-    (loss [] fp32, dlogits [N, C] fp32): one segmented radix sort of the [C, N] error matrix."""
+    (loss [] fp32, dlogits [N, C] fp32).  C <= 64 without a handle: one segmented radix sort of the dense [C, N] error matrix.
+    65 <= C <= 1024, or any C with `present` (lovasz_present of the same target): the sort runs over the P classes present only
+    ([P, N], ~56 B x P x N of workspace); without a handle one is made here, and reading P is this path's one host synchronisation.
+    A handle of another target (or of this one edited in place since), class count or ignore_index is refused before any launch."""
     require_cuda(logits, target)
     if target.dtype != torch.int64:
         raise PtcoreError("target must be int64")
     lg, rs = _rows_view(logits)
     n, c = lg.shape
+    if present is None and c > LOVASZ_DENSE_MAX_C:
+        if c > LOVASZ_MAX_C:
+            raise PtcoreError(f"lovasz_softmax: unsupported shape [{n}, {c}] (at most {LOVASZ_MAX_C} classes)")
+        present = lovasz_present(target, c, ignore_index)
+    if present is not None:
+        return _lovasz_softmax_rows(lg, rs, target, ignore_index, present)
     nbytes = lib().ptc_lovasz_softmax_workspace_bytes(n, c)
     if nbytes == 0:
-        raise PtcoreError(f"lovasz_softmax: unsupported shape [{n}, {c}] (at most 64 classes)")
+        raise PtcoreError(f"lovasz_softmax: unsupported shape [{n}, {c}]")
     ws = _ws(nbytes, lg.device)
     loss = torch.empty((), dtype=torch.float32, device=lg.device)
     dlogits = torch.empty((n, c), dtype=torch.float32, device=lg.device)
     check(lib().ptc_lovasz_softmax(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), int(ignore_index), ptr(loss),
                                    ptr(dlogits), ptr(ws), nbytes, stream_ptr()), "ptc_lovasz_softmax")
+    return loss, dlogits
+
+
+def _lovasz_softmax_rows(lg, rs, target, ignore_index, present):
+    n, c = lg.shape
+    if not isinstance(present, LovaszPresent):
+        raise PtcoreError("lovasz_softmax: `present` must come from lovasz_present")
+    if c > LOVASZ_MAX_C or c < 1:
+        raise PtcoreError(f"lovasz_softmax: unsupported shape [{n}, {c}] (at most {LOVASZ_MAX_C} classes)")
+    if target.dim() != 1 or target.shape[0] != n:
+        raise PtcoreError("lovasz_softmax: target must be [N]")
+    if not present.matches(target, c, ignore_index):
+        raise PtcoreError("lovasz_softmax: `present` was made from another target (or the target was edited in place since), "
+                          "another number of classes or another ignore_index")
+    rows = present.rows()
+    if not 0 <= rows <= c:
+        raise PtcoreError(f"lovasz_softmax: {rows} present classes of {c}")
+    nbytes = lib().ptc_lovasz_softmax_rows_workspace_bytes(n, c, rows)
+    ws = _ws(nbytes, lg.device)
+    loss = torch.empty((), dtype=torch.float32, device=lg.device)
+    dlogits = torch.empty((n, c), dtype=torch.float32, device=lg.device)
+    check(lib().ptc_lovasz_softmax_rows(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), int(ignore_index), ptr(present.class_count),
+                                        ptr(present.row_of), ptr(present.class_of), ptr(present.n_present), rows, ptr(loss), ptr(dlogits),
+                                        ptr(ws), nbytes, stream_ptr()), "ptc_lovasz_softmax_rows")
     return loss, dlogits
 
 

@@ -28,7 +28,9 @@ from .structure import Point, batch2offset, offset2batch
 
 class _Criteria:
     """build_criteria(criteria) of point_group_v1m2 (losses/builder.py:22-31) on the engine's loss kernels: CrossEntropyLoss and
-    multiclass LovaszLoss with the reference's default settings (losses/misc.py, losses/lovasz.py); other settings raise"""
+    multiclass LovaszLoss with the reference's default settings (losses/misc.py, losses/lovasz.py); other settings raise.  Both serve up
+    to 1024 classes; above 64 LovaszLoss sorts the classes present only (functional.lovasz_softmax: ~56 B x present classes x points of
+    workspace and one host read of their number per call)"""
 
     SUPPORTED = {
         "CrossEntropyLoss": ("cross_entropy", dict(weight=None, size_average=None, reduce=None, reduction="mean", label_smoothing=0.0)),

@@ -15,6 +15,8 @@ import torch.nn as nn
 
 from . import functional as PF
 from . import nn as PNN
+from . import ops
+from ._lib import PtcoreError
 from .structure import Point
 
 
@@ -29,15 +31,33 @@ class DefaultSegmentorV2(nn.Module):
         self.seg_head = PNN.Linear(backbone_out_channels, num_classes) if num_classes > 0 else nn.Identity()
         self.backbone = backbone
         self.ignore_index = ignore_index
+        self.num_classes = int(num_classes)
 
-    def criteria(self, seg_logits, segment):   # GPU only, like every op of the engine
+    def criteria(self, seg_logits, segment, present=None):   # GPU only, like every op of the engine
         loss = 0
         for name, w in zip(self.criteria_names, self.loss_weights):
-            fn = PF.cross_entropy if name == "ce" else PF.lovasz_softmax
-            loss = loss + fn(seg_logits, segment, self.ignore_index) * w
+            if name == "lovasz" and present is not None:
+                term = PF.lovasz_softmax(seg_logits, segment, self.ignore_index, present=present)
+            else:
+                term = (PF.cross_entropy if name == "ce" else PF.lovasz_softmax)(seg_logits, segment, self.ignore_index)
+            loss = loss + term * w
         return loss
 
+    def _lovasz_present(self, input_dict):
+        """More than 64 classes: the Lovasz kernels sort the classes present only and the host has to know how many.  Asked for
+        here, BEFORE the backbone is enqueued, the count is in host memory long before the loss needs it -- the host keeps its
+        lead over the device."""
+        segment = input_dict["segment"] if "segment" in input_dict.keys() else None
+        if "lovasz" not in self.criteria_names or self.num_classes <= ops.LOVASZ_DENSE_MAX_C or not torch.is_tensor(segment):
+            return None
+        try:
+            ops.require_cuda(segment)           # labels the ops would not take (CPU tensors): nothing to ask for
+        except PtcoreError:
+            return None
+        return PF.lovasz_present(segment, self.num_classes, self.ignore_index)
+
     def forward(self, input_dict, return_point=False):
+        present = self._lovasz_present(input_dict)
         point = Point(input_dict)
         point = self.backbone(point)
         if isinstance(point, Point):
@@ -54,9 +74,9 @@ class DefaultSegmentorV2(nn.Module):
         if return_point:
             return_dict["point"] = point
         if self.training:
-            return_dict["loss"] = self.criteria(seg_logits, input_dict["segment"])
+            return_dict["loss"] = self.criteria(seg_logits, input_dict["segment"], present)
         elif "segment" in input_dict.keys():
-            return_dict["loss"] = self.criteria(seg_logits, input_dict["segment"])
+            return_dict["loss"] = self.criteria(seg_logits, input_dict["segment"], present)
             return_dict["seg_logits"] = seg_logits
         else:
             return_dict["seg_logits"] = seg_logits
@@ -68,8 +88,6 @@ def semseg_eval_counts(seg_logits, input_dict, num_classes: int, ignore_index: i
     pred = seg_logits.max(1)[1]; with `inverse` / `origin_segment` in the batch (GridSample test mode) predictions are
     carried back to the original points; then intersection_and_union_gpu (pointcept/utils/misc.py:57-69).
     Returns (intersection, union, target), int64 [num_classes] on the device -- ready for the evaluator's all_reduce."""
-    from . import ops
-
     if "inverse" in input_dict.keys():
         assert "origin_segment" in input_dict.keys()
         return ops.seg_eval_hist(seg_logits, input_dict["origin_segment"], num_classes, ignore_index, inverse=input_dict["inverse"])

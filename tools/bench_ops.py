@@ -288,6 +288,56 @@ def bench_losses(rows, results, n=819200, c=20):
                 f"({r['lovasz_GBps']:.0f} GB/s of ~190 B/slot) | ATen softmax + {c} sorts + cumsums alone {r['aten_sorts_only_us']:.1f} us")
 
 
+def bench_losses_wide(rows, results, n=819200):
+    """Lovasz-Softmax over the classes present only (ops.lovasz_present + the rows path): the ScanNet200 shape (200 classes, ~60 in
+    the batch) against the torch expression of the criterion (oracle.losses.lovasz_softmax_torch, forward + backward) on the same
+    device, and the 20-class BASELINE shape through both paths, with no class absent and with half of them absent."""
+    from oracle.losses import lovasz_softmax_torch
+
+    def med(fn, iters, warm, reps=3):      # median [min .. max] of `reps` event-timed batches, seconds
+        t = sorted(timeit(fn, iters, warm if k == 0 else 0) for k in range(reps))
+        return t[len(t) // 2], t[0], t[-1]
+
+    fmt = lambda t: f"{t[0] * 1e6:.1f} [{t[1] * 1e6:.1f} .. {t[2] * 1e6:.1f}] us"  # noqa: E731
+    g = torch.Generator().manual_seed(0)
+    c = 200
+    logits = torch.randn(n, c, generator=g).to(torch.bfloat16).to(DEV)
+    y = torch.randint(0, 60, (n,), generator=g) * 3
+    y[torch.rand(n, generator=g) < 0.05] = -1
+    y = y.to(DEV)
+    h = ops.lovasz_present(y, c, -1)
+    p = h.rows()
+    t_h = med(lambda: ops.lovasz_present(y, c, -1), 10, 2)
+    t_rows = med(lambda: ops.lovasz_softmax(logits, y, -1, present=h), 5, 2)
+
+    def torch_expr():
+        x = logits.detach().requires_grad_(True)
+        lovasz_softmax_torch(x, y, -1).backward()
+        return x.grad
+
+    t_torch = med(torch_expr, 2, 1)
+    r = {"n": n, "c": c, "present": p, "lovasz_present_us": [round(v * 1e6, 1) for v in t_h], "lovasz_rows_us": [round(v * 1e6, 1) for v in t_rows],
+         "torch_expression_fwd_bwd_us": [round(v * 1e6, 1) for v in t_torch], "rows_GBps": round(190.0 * n * p / t_rows[0] / 1e9, 1)}
+    results.append(r)
+    rows.append(f"losses wide [{n} x {c}] bf16, {p} classes present, median [min .. max] of 3: lovasz_present {fmt(t_h)} | Lovasz rows path fwd+grad "
+                f"{fmt(t_rows)} ({r['rows_GBps']:.0f} GB/s of ~190 B per (present class, point) slot) | torch expression fwd+bwd "
+                f"{fmt(t_torch)} ({t_torch[0] / t_rows[0]:.1f}x)")
+    del logits
+    c = 20
+    wide = torch.randn(n, 32, generator=g).to(torch.bfloat16).to(DEV)
+    lg = wide[:, :c]
+    for used in (c, c // 2):
+        y = torch.randint(-1, used, (n,), generator=g).to(DEV)
+        h = ops.lovasz_present(y, c, -1)
+        t_dense = med(lambda: ops.lovasz_softmax(lg, y, -1), 10, 2)
+        t_rows = med(lambda: ops.lovasz_softmax(lg, y, -1, present=h), 10, 2)
+        r = {"n": n, "c": c, "present": h.rows(), "lovasz_dense_us": [round(v * 1e6, 1) for v in t_dense],
+             "lovasz_rows_us": [round(v * 1e6, 1) for v in t_rows]}
+        results.append(r)
+        rows.append(f"losses wide [{n} x {c}] bf16, {r['present']} classes present, median [min .. max] of 3: Lovasz dense path {fmt(t_dense)} | rows path "
+                    f"(handle made ahead) {fmt(t_rows)} (dense / rows = {t_dense[0] / t_rows[0]:.2f})")
+
+
 def bench_front_end(rows, results):
     """the 8(f) rows: device GridSample on a raw 2M-point scan, kNN at the evaluator's shape (predictions of a 100k-voxel
     scene carried to its 250k raw points, evaluator.py:569), k = 16 self-query, farthest point sampling 100k -> 2048."""
@@ -491,7 +541,7 @@ def bench_oacnns(rows, results, dt=torch.bfloat16):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default="", help="comma list of sections: linear,ln,attn,attn_hd,spconv,stages,losses,front (opt-in: oacnns, ...)")
+    ap.add_argument("--only", default="", help="comma list of sections: linear,ln,attn,attn_hd,spconv,stages,losses,losses_wide,front (opt-in: oacnns, ...)")
     args = ap.parse_args()
     only = set(x for x in args.only.split(",") if x)
     want = lambda name: not only or name in only  # noqa: E731
@@ -572,6 +622,9 @@ def main():
                 bench_linear(rows, n, cin, cout, res["linear"])
     if want("losses"):
         bench_losses(rows, res["losses"])
+    if want("losses_wide"):
+        res["losses_wide"] = []
+        bench_losses_wide(rows, res["losses_wide"])
     if want("front"):
         bench_front_end(rows, res["front"])
     print("\n".join(rows))

@@ -29,7 +29,8 @@ def child(what, k, scenes, points, reps):
 
     dev = torch.device("cuda")
     torch.manual_seed(0)
-    # the engine's Lovasz kernel takes at most 64 classes: above that the criteria are the cross entropy alone (both sides alike)
+    # above 64 classes the criteria are the cross entropy alone (both sides alike), as when profiles/cac_ops.txt was taken: the engine's
+    # Lovasz kernels stopped at 64 classes then
     model = CACSegmentor(num_classes=k, backbone_out_channels=96, backbone=BACKBONE, criteria=CRITERIA if k <= 64 else CRITERIA[:1],
                          conf_thresh=0.75).to(dev)
     opt = torch.optim.SGD(model.parameters(), lr=0.1, momentum=0.9, nesterov=True)
@@ -114,7 +115,7 @@ def main():
     lines = [f"CAC-v1m1, ScanNet config shape: {a.scenes} scenes x {a.points} points before voxelisation (the size after it is on every "
              f"line), C = 96, fp32, SpUNet base channels, conf_thresh 0.75; median [min .. max] of {a.reps} alternating repeats, ms, each one "
              f"event-timed call (the three stages forward + backward) including its host reads; comparison side = PTC_CAC=0 on the same build; "
-             f"criteria CrossEntropy + Lovasz, above 64 classes CrossEntropy alone (the limit of the engine's Lovasz kernel)"]
+             f"criteria CrossEntropy + Lovasz, above 64 classes CrossEntropy alone (as in profiles/cac_ops.txt)"]
     stop = False
     for k in a.classes:
         for what in STAGES:
