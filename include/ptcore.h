@@ -898,6 +898,49 @@ int ptc_cac_distill_fwd(const float* pred, const float* soft, const int64_t* tar
 int ptc_cac_distill_bwd(const float* pred, const float* soft, const int64_t* target, int64_t n, int k, float smoothness, float eps,
                         const float* stats, const float* dloss, float* dpred, ptc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SGIFormer-v1m1 query decoder (csrc/sgiformer.hip; pointcept/models/sgiformer/sgiformer_v1m1_base.py, loss.py).
+ * A ragged batch of s scenes: cu_q, cu_k, cu_g are int32 [s + 1] row starts of the queries, the keys (superpoints) and the
+ * instances.  "Packed" masks hold one bit per (row, column) in uint32 words, ceil(columns / 32) words per row, bit c % 32 of word
+ * c / 32; the rows of scene i start at word row_off[i] (int64 [s]).  No float atomics anywhere: bit-reproducible.
+ *
+ * Attention: q, out, dout, dq [tq, h, d], k, v, dk, dv [tk, h, d], dtype PTC_F32 or PTC_BF16; d = 32 only (PTC_EUNSUPPORTED
+ *   otherwise; see the _supported entry).  Scene i attends its queries to its keys: out = softmax(scale q k^T + mask) v with bf16 MFMA
+ *   operands (bf16 rows: one MFMA per product; fp32 rows: every operand as two bf16 terms, three MFMAs per product, operand error
+ *   2^-17), fp32 accumulation and softmax, an online softmax over key tiles; lse [tq, h] fp32 = the row log-sum-exp of the scaled
+ *   scores.  mask (or NULL): packed [Lq_i, Lk_i], a SET bit = masked out, shared by the heads; bits past Lk_i are ignored.  The
+ *   kernels ASSUME that no row is fully masked (the pack entry below guarantees it); such a row gives zeros and lse = -inf rather than
+ *   the NaN of a dense softmax.  The backward recomputes the probabilities; dk / dv are reduced per key row over the query tiles in
+ *   index order.  Nothing of size Lq x Lk is written to memory.  workspace: tq * h floats.
+ * Mask pack: logits = the [Lq_i, M_i] fp32 mask logits of scene i at element logit_off[i] (M_i from cu_k); bit = sigmoid(x) < 0.5,
+ *   a row whose bits would all be set is cleared (forward_head, :372-378).  One launch for all scenes.
+ * Match cost: cost [Lq_i, G_i] at element cost_off[i] = w_cls (-softmax(cls)[:, gt_cls]) + w_bce BCE + w_dice dice (loss.py:15-52:
+ *   BCE / M_i, dice with +1 above and below) from the mask logits, cls [tq, c] and the packed ground-truth masks [G_i, M_i] of the
+ *   targets entry; fp32 in and out, sums in double.  A row with a non-finite logit, and any non-finite entry, is 1e6.  No backward.
+ * Targets (prepare_target, :517-585): from per-point instance, segment, sp_inverse (global superpoint row) and offset [s], with
+ *   G_i = max instance + 1 of scene i: sp_size [total_sp], counts [G_i, M_i] int32 at cnt_off[i], packed gt masks at word_off[i]
+ *   (int64 [s + 1]) with bit = 2 count > superpoint size, inst_cls [total_inst] = max segment over the instance's points (0 for an id
+ *   no point carries).  Points with instance < 0 count towards the superpoint size and nothing else.
+ * ------------------------------------------------------------------------------------------ */
+int ptc_sgi_attn_supported(int d);
+size_t ptc_sgi_attn_workspace_bytes(int64_t tq, int h);
+int ptc_sgi_attn_fwd(const void* q, const void* k, const void* v, int dtype, const int32_t* cu_q, const int32_t* cu_k, int s, int64_t tq,
+                     int64_t tk, int h, int d, const uint32_t* mask, const int64_t* mask_row_off, float scale, void* out, float* lse,
+                     ptc_stream_t stream);
+int ptc_sgi_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, int dtype,
+                     const int32_t* cu_q, const int32_t* cu_k, int s, int64_t tq, int64_t tk, int h, int d, const uint32_t* mask,
+                     const int64_t* mask_row_off, float scale, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes,
+                     ptc_stream_t stream);
+int ptc_sgi_pack_mask(const float* logits, const int64_t* logit_off, const int32_t* cu_q, const int32_t* cu_k, int s, int64_t tq,
+                      const int64_t* mask_row_off, uint32_t* words, ptc_stream_t stream);
+int ptc_sgi_match_cost(const float* logits, const int64_t* logit_off, const float* cls, int c, const int32_t* cu_q, const int32_t* cu_k,
+                       const int32_t* cu_g, int s, int64_t tq, const uint32_t* gt_words, const int64_t* gt_word_off, const int64_t* gt_cls,
+                       const int64_t* cost_off, float w_cls, float w_bce, float w_dice, float* cost, ptc_stream_t stream);
+int ptc_sgi_targets(const int64_t* instance, const int64_t* segment, const int64_t* sp_inverse, const int64_t* offset, int s, int64_t n,
+                    const int32_t* cu_k, const int32_t* cu_g, const int64_t* cnt_off, const int64_t* word_off, int64_t total_sp,
+                    int64_t total_inst, int64_t total_counts, int64_t total_words, int32_t* sp_size, int32_t* counts, uint32_t* gt_words,
+                    int64_t* inst_cls, ptc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,17 @@ _SIGNATURES = {
     "ptc_cac_distill_workspace_bytes": (c_size, [c_i64, c_int]),
     "ptc_cac_distill_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "ptc_cac_distill_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "ptc_sgi_attn_supported": (c_int, [c_int]),
+    "ptc_sgi_attn_workspace_bytes": (c_size, [c_i64, c_int]),
+    "ptc_sgi_attn_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_f32, c_ptr, c_ptr,
+                                 c_ptr]),
+    "ptc_sgi_attn_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr,
+                                 c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_sgi_pack_mask": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
+    "ptc_sgi_match_cost": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_f32,
+                                   c_ptr, c_ptr]),
+    "ptc_sgi_targets": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr,
+                                c_ptr, c_ptr, c_ptr]),
     "ptc_lovasz_softmax_workspace_bytes": (c_size, [c_i64, c_int]),
     "ptc_lovasz_softmax": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "ptc_lovasz_present": (c_int, [c_ptr, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),

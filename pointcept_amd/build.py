@@ -55,6 +55,7 @@ HIP_SOURCES = [
     "pg_cluster.hip",
     "msc.hip",
     "cac.hip",
+    "sgiformer.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

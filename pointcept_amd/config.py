@@ -40,6 +40,9 @@ settings), and so a regression can be bisected without a rebuild.
   PTC_CAC=0          the context-aware classifier's prototype pooling, cosine classifier and distillation loss
                      (context_aware_classifier.py) run as the reference's own expression -- per-class and per-scene loops, dense
                      softmax / one-hot temporaries, library GEMMs -- instead of csrc/cac.hip (A/B baseline, and the CPU path of the port)
+  PTC_SGI=0          SGIFormer's decoder attention, attention-mask packing, matcher cost and target builder (sgiformer.py) run as the
+                     reference's own expression -- a Python loop over scenes, dense [heads, Lq, Lk] probabilities, [Lq, M] BCE maps,
+                     an [N, instances] one-hot -- instead of csrc/sgiformer.hip (A/B baseline, and the CPU path of the port)
   PTC_FUSE_BLOCK=0   the three residual joints of a PTv3 Block run as separate LayerNorm / add / cast
                      kernels instead of the fused add_norm passes
 """
@@ -68,6 +71,7 @@ OACNN_AGG = _flag("PTC_OACNN_AGG", True)
 PG_CLUSTER = _flag("PTC_PG_CLUSTER", True)
 MSC_KERNELS = _flag("PTC_MSC", True)
 CAC_KERNELS = _flag("PTC_CAC", True)
+SGI_KERNELS = _flag("PTC_SGI", True)
 WGRAD_BLK = _flag("PTC_WGRAD_BLK", True)
 FUSE_BN_TAIL = _flag("PTC_FUSE_BN_TAIL", True)
 BATCH_BN_COUNTERS = _flag("PTC_BATCH_BN_COUNTERS", True)

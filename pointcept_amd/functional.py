@@ -1599,3 +1599,242 @@ def cac_distill_torch(pred, soft, target, smoothness: float = 0.5, eps: float = 
     if len(weight_list) > 0:
         return sum(loss_list) / (sum(weight_list) + 1e-4)
     return torch.zeros(1, dtype=pred.dtype, device=pred.device).mean()
+
+
+# ------------------------------------------------------------------------------------------------
+# SGIFormer decoder (sgiformer_v1m1_base.py, loss.py): ragged masked attention, attention-mask packing, matcher cost, targets.
+# Each function runs csrc/sgiformer.hip, or its *_torch twin -- the reference's own expression, loops included -- for CPU tensors, for
+# shapes the kernels refuse, and under PTC_SGI=0 (config.SGI_KERNELS).  `use_kernels` overrides the choice.
+# ------------------------------------------------------------------------------------------------
+def _sgi_use_kernels(t: torch.Tensor, use_kernels) -> bool:
+    return bool(config.SGI_KERNELS and t.is_cuda) if use_kernels is None else bool(use_kernels)
+
+
+def sgi_pack_bits(b: torch.Tensor) -> torch.Tensor:
+    """bool [R, M] -> int32 words [R, ceil(M / 32)], bit c % 32 of word c / 32"""
+    r, m = b.shape
+    w = (m + 31) // 32
+    x = torch.zeros((r, w * 32), dtype=torch.int64, device=b.device)
+    x[:, :m] = b.to(torch.int64)
+    x = (x.view(r, w, 32) << torch.arange(32, device=b.device)).sum(-1)
+    return torch.where(x >= 2 ** 31, x - 2 ** 32, x).to(torch.int32)
+
+
+def sgi_unpack_bits(words: torch.Tensor, m: int) -> torch.Tensor:
+    """int32 words [R, ceil(M / 32)] -> bool [R, M]"""
+    r = words.shape[0]
+    bits = (words.to(torch.int64).unsqueeze(-1) >> torch.arange(32, device=words.device)) & 1
+    return bits.reshape(r, words.shape[1] * 32)[:, :m].bool()
+
+
+class SGIPacked:
+    """One bit per (row, column) of the [rows_i, cols_i] blocks of a ragged batch: `words` int32, ceil(cols_i / 32) words per row, the
+    rows of scene i from word off[i] (`off` int64 [S + 1] on the device).  Attention masks (set = masked out) and ground-truth
+    instance masks share it."""
+
+    def __init__(self, words, off, rows, cols):
+        self.words, self.off, self.rows, self.cols = words, off, [int(r) for r in rows], [int(c) for c in cols]
+
+    @staticmethod
+    def from_bool(masks):
+        rows, cols = [m.shape[0] for m in masks], [m.shape[1] for m in masks]
+        dev = masks[0].device
+        off, _ = ops.sgi_offsets(rows, cols, dev, True)
+        words = torch.cat([sgi_pack_bits(m).reshape(-1) for m in masks]) if masks else torch.empty(0, dtype=torch.int32, device=dev)
+        return SGIPacked(words, off, rows, cols)
+
+    def to_bool(self):
+        out, at = [], 0
+        for r, c in zip(self.rows, self.cols):
+            w = (c + 31) // 32
+            out.append(sgi_unpack_bits(self.words[at:at + r * w].view(r, w), c))
+            at += r * w
+        return out
+
+
+class _SGIAttention(Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, words, row_off, scale):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = ops.sgi_attn_fwd(q, k, v, cu_q, cu_k, words, row_off, scale)
+        ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k)
+        ctx.mask = (words, row_off)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
+        dq, dk, dv = ops.sgi_attn_bwd(q, k, v, out, dout, lse, cu_q, cu_k, ctx.mask[0], ctx.mask[1], ctx.scale)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def sgi_attention(q, k, v, lq, lk, mask=None, scale=None, use_kernels=None):
+    """Multi-head attention of every scene of a ragged batch in one launch: q [Tq, H, D], k, v [Tk, H, D]; scene i attends its lq[i]
+    query rows to its lk[i] key rows (host lists).  mask: an SGIPacked [lq_i, lk_i] or a list of bool [lq_i, lk_i], True / set =
+    masked out, shared by the heads, no row fully masked.  fp32 or bf16 rows (other dtypes are computed in fp32); bf16 MFMA operands,
+    fp32 accumulation and softmax; nothing of size Lq x Lk is written to memory.  D = 32 on the kernels, other head dims on torch."""
+    if not (_sgi_use_kernels(q, use_kernels) and ops.sgi_attn_supported(q.shape[-1])):
+        return sgi_attention_torch(q, k, v, lq, lk, mask, scale)
+    if mask is not None and not isinstance(mask, SGIPacked):
+        mask = SGIPacked.from_bool(mask)
+    dt = q.dtype if q.dtype in (torch.float32, torch.bfloat16) else torch.float32
+    cu_q, cu_k = ops.sgi_cu(lq, q.device), ops.sgi_cu(lk, q.device)
+    words, row_off = (None, None) if mask is None else (mask.words, mask.off)
+    with torch.autocast(device_type=q.device.type, enabled=False):
+        out = _SGIAttention.apply(q.to(dt), k.to(dt), v.to(dt), cu_q, cu_k, words, row_off, scale)
+    return out.to(q.dtype)
+
+
+def sgi_attention_torch(q, k, v, lq, lk, mask=None, scale=None):
+    """nn.MultiheadAttention's own arithmetic (need_weights=True path: scaled q, additive -inf mask, dense softmax, bmm), one scene
+    after the other as CrossAttentionLayer / SelfAttentionLayer (:208-248) loop"""
+    if isinstance(mask, SGIPacked):
+        mask = mask.to_bool()
+    scale = float(q.shape[-1]) ** -0.5 if scale is None else float(scale)
+    outs, aq, ak = [], 0, 0
+    for i, (nq, nk) in enumerate(zip(lq, lk)):
+        qi = (q[aq:aq + nq] * scale).transpose(0, 1)         # [H, Lq, D]
+        ki, vi = k[ak:ak + nk].transpose(0, 1), v[ak:ak + nk].transpose(0, 1)
+        if mask is not None:
+            bias = torch.zeros(mask[i].shape, dtype=qi.dtype, device=qi.device).masked_fill_(mask[i], float("-inf"))
+            attn = torch.baddbmm(bias.unsqueeze(0).expand(qi.shape[0], -1, -1), qi, ki.transpose(-2, -1))
+        else:
+            attn = torch.bmm(qi, ki.transpose(-2, -1))
+        attn = F.softmax(attn, dim=-1)
+        outs.append(torch.bmm(attn, vi).transpose(0, 1))
+        aq, ak = aq + nq, ak + nk
+    return torch.cat(outs, 0)
+
+
+def sgi_pack_mask(logits, use_kernels=None):
+    """The attention masks of forward_head (:372-378) for every scene in one launch: logits = list of [lq_i, M_i] mask logits ->
+    SGIPacked with a bit set where sigmoid(x) < 0.5, rows whose bits would all be set cleared.  Not differentiable."""
+    if not _sgi_use_kernels(logits[0], use_kernels):
+        return SGIPacked.from_bool(sgi_pack_mask_torch(logits))
+    lq, lk = [x.shape[0] for x in logits], [x.shape[1] for x in logits]
+    flat = torch.cat([x.detach().float().reshape(-1) for x in logits])
+    words, row_off = ops.sgi_pack_mask(flat, lq, lk)
+    return SGIPacked(words, row_off, lq, lk)
+
+
+def sgi_pack_mask_torch(logits):
+    out = []
+    for pred_mask_ in logits:
+        attn_mask_ = (pred_mask_.sigmoid() < 0.5).bool()
+        attn_mask_[torch.where(attn_mask_.sum(-1) == attn_mask_.shape[-1])] = False
+        out.append(attn_mask_.detach())
+    return out
+
+
+def sgi_match_cost(mask_logits, cls_logits, gt_masks, gt_cls, weights=(0.5, 1.0, 1.0), use_kernels=None):
+    """The Hungarian matcher's cost matrices of every scene of a level in one launch (loss.py:331-429):
+    w_cls (-softmax(cls)[:, gt_cls]) + w_bce BCE + w_dice dice, non-finite entries replaced by 1e6.  mask_logits: list of
+    [lq_i, M_i]; cls_logits: list of [lq_i, C]; gt_masks: SGIPacked [G_i, M_i] (or a list of bool); gt_cls: list of int64 [G_i].
+    -> list of fp32 [lq_i, G_i].  No gradient (the reference runs it under no_grad)."""
+    with torch.no_grad():
+        if not _sgi_use_kernels(mask_logits[0], use_kernels):
+            return sgi_match_cost_torch(mask_logits, cls_logits, gt_masks, gt_cls, weights)
+        if not isinstance(gt_masks, SGIPacked):
+            gt_masks = SGIPacked.from_bool(gt_masks)
+        lq, lk, g = [x.shape[0] for x in mask_logits], [x.shape[1] for x in mask_logits], [int(c.numel()) for c in gt_cls]
+        flat = torch.cat([x.float().reshape(-1) for x in mask_logits])
+        cost, off = ops.sgi_match_cost(flat, torch.cat([c.float() for c in cls_logits]), lq, lk, g, gt_masks.words, gt_masks.off,
+                                       torch.cat([c.to(torch.int64) for c in gt_cls]), weights)
+        return [cost[off[i]:off[i + 1]].view(lq[i], g[i]) for i in range(len(lq))]
+
+
+def sgi_match_cost_torch(mask_logits, cls_logits, gt_masks, gt_cls, weights=(0.5, 1.0, 1.0)):
+    if isinstance(gt_masks, SGIPacked):
+        gt_masks = gt_masks.to_bool()
+    out = []
+    for inputs, cls, targets, inst_cls in zip(mask_logits, cls_logits, gt_masks, gt_cls):
+        inputs, targets = inputs.float(), targets.float()
+        score = cls.softmax(-1)
+        cost_cls = -score[:, inst_cls.long()] * weights[0]
+        pos = F.binary_cross_entropy_with_logits(inputs, torch.ones_like(inputs), reduction="none")
+        neg = F.binary_cross_entropy_with_logits(inputs, torch.zeros_like(inputs), reduction="none")
+        pos_loss = torch.einsum("nc,mc->nm", pos, targets)
+        neg_loss = torch.einsum("nc,mc->nm", neg, (1 - targets))
+        cost_bce = (pos_loss + neg_loss) / inputs.shape[1] * weights[1]
+        sig = inputs.sigmoid()
+        numerator = 2 * torch.einsum("nc,mc->nm", sig, targets)
+        denominator = sig.sum(-1)[:, None] + targets.sum(-1)[None, :]
+        cost_dice = (1 - (numerator + 1) / (denominator + 1)) * weights[2]
+        cost_value = torch.stack([cost_cls, cost_bce, cost_dice]).sum(dim=0)
+        cost_value = torch.where(torch.isnan(cost_value) | torch.isinf(cost_value), torch.full_like(cost_value, 1e6), cost_value)
+        out.append(cost_value)
+    return out
+
+
+class SGITargets:
+    """prepare_target's instance information of a batch: counts (list of int32 [G_i, M_i]: points of instance g in superpoint m),
+    masks (SGIPacked [G_i, M_i]: 2 count > superpoint size), cls (list of int64 [G_i]); G_i = max instance + 1, 0 without any."""
+
+    def __init__(self, counts, masks, cls):
+        self.counts, self.masks, self.cls = counts, masks, cls
+
+
+def _sgi_scene_sizes(instance, sp_inverse, offset):
+    """host (bounds, superpoints per scene, instances per scene) with ONE device -> host copy"""
+    ends = offset.to(torch.int64)
+    s = ends.numel()
+    if instance.numel() == 0:
+        return [(0, 0)] * s, [0] * s, [0] * s
+    starts = torch.cat([ends.new_zeros(1), ends[:-1]])
+    seg = torch.repeat_interleave(torch.arange(s, device=ends.device), ends - starts)
+    imax = torch.full((s,), -1, dtype=torch.int64, device=ends.device).scatter_reduce_(0, seg, instance.to(torch.int64), "amax")
+    smax = torch.full((s,), -1, dtype=torch.int64, device=ends.device).scatter_reduce_(0, seg, sp_inverse.to(torch.int64), "amax")
+    smin = torch.full((s,), 2 ** 62, dtype=torch.int64, device=ends.device).scatter_reduce_(0, seg, sp_inverse.to(torch.int64), "amin")
+    host = torch.stack([ends, imax, smin, smax]).tolist()
+    bounds = list(zip([0] + host[0][:-1], host[0]))
+    lk = [int(b - a + 1) if b >= a else 0 for a, b in zip(host[2], host[3])]
+    g = [max(int(m) + 1, 0) for m in host[1]]
+    return bounds, lk, g
+
+
+def sgi_targets(instance, segment, sp_inverse, offset, use_kernels=None) -> SGITargets:
+    """prepare_target (:538-584) for all scenes in one pass, without the [N, G] one-hot.  instance, segment (already remapped),
+    sp_inverse (the global superpoint row of each point, rows grouped by scene) per point; offset [S].  Points with instance < 0
+    count towards the size of their superpoint and towards nothing else (the reference's scatter-max indexes with -1 there, which the
+    CUDA library leaves undefined: such rows are skipped, here and in the golden generator)."""
+    with torch.no_grad():
+        if not _sgi_use_kernels(instance, use_kernels):
+            return sgi_targets_torch(instance, segment, sp_inverse, offset)
+        _, lk, g = _sgi_scene_sizes(instance, sp_inverse, offset)
+        _, counts, words, word_off, inst_cls = ops.sgi_targets(instance, segment, sp_inverse, offset, lk, g)
+        cl, il, ac, ai = [], [], 0, 0
+        for gi, mi in zip(g, lk):
+            cl.append(counts[ac:ac + gi * mi].view(gi, mi))
+            il.append(inst_cls[ai:ai + gi])
+            ac, ai = ac + gi * mi, ai + gi
+        return SGITargets(cl, SGIPacked(words, word_off, g, lk), il)
+
+
+def sgi_targets_torch(instance, segment, sp_inverse, offset) -> SGITargets:
+    ends = [int(e) for e in offset.tolist()]
+    counts, masks, cls = [], [], []
+    for start, end in zip([0] + ends[:-1], ends):
+        instance_, segment_ = instance[start:end].long(), segment[start:end].long()
+        sp_inverse_ = sp_inverse[start:end].long()
+        sp_inverse_ = sp_inverse_ - sp_inverse_.min()
+        m = int(sp_inverse_.max()) + 1
+        if instance_.max() >= 0:
+            inst_onehot_ = torch.zeros((instance_.shape[0], int(instance_.max()) + 1), device=instance_.device, dtype=instance_.dtype)
+            inst_mask_ = instance_ != -1
+            inst_onehot_[inst_mask_] = F.one_hot(instance_[inst_mask_], inst_onehot_.shape[1])
+            count_ = torch.zeros((m, inst_onehot_.shape[1]), device=instance_.device, dtype=instance_.dtype).index_add_(0, sp_inverse_, inst_onehot_)
+            size_ = torch.bincount(sp_inverse_, minlength=m)
+            inst_sp_mask_ = (count_.double() / size_.clamp(min=1).unsqueeze(1)).T > 0.5
+            inst_cls_ = torch.full((inst_onehot_.shape[1],), torch.iinfo(torch.int64).min, device=instance_.device, dtype=torch.int64)
+            inst_cls_ = inst_cls_.scatter_reduce(0, instance_[inst_mask_], segment_[inst_mask_], "amax")
+            inst_cls_[inst_cls_ == torch.iinfo(torch.int64).min] = 0
+            counts.append(count_.T.to(torch.int32).contiguous())
+        else:
+            inst_sp_mask_ = torch.zeros((0, m), device=instance_.device, dtype=torch.bool)
+            inst_cls_ = torch.zeros(0, device=instance_.device, dtype=torch.int64)
+            counts.append(torch.zeros((0, m), device=instance_.device, dtype=torch.int32))
+        masks.append(inst_sp_mask_)
+        cls.append(inst_cls_)
+    return SGITargets(counts, SGIPacked.from_bool(masks), cls)

@@ -1975,3 +1975,140 @@ def cac_distill_bwd(state, smoothness: float, eps: float, stats, dloss):
     check(lib().ptc_cac_distill_bwd(ptr(pred), ptr(soft), ptr(tg), n, k, float(smoothness), float(eps), ptr(stats), ptr(g), ptr(dpred),
                                     stream_ptr()), "ptc_cac_distill_bwd")
     return dpred
+
+
+# ------------------------------------------------------------------------------------------------
+# SGIFormer decoder (csrc/sgiformer.hip): ragged masked attention, mask bit-pack, matcher cost, target builder
+# ------------------------------------------------------------------------------------------------
+def sgi_attn_supported(d: int) -> bool:
+    return bool(lib().ptc_sgi_attn_supported(int(d)))
+
+
+def sgi_cu(lengths: Sequence[int], device) -> torch.Tensor:
+    """int32 [S + 1] row starts of a ragged batch from its host lengths"""
+    cu = [0]
+    for n in lengths:
+        cu.append(cu[-1] + int(n))
+    return torch.tensor(cu, dtype=torch.int32, device=device)
+
+
+def sgi_offsets(rows: Sequence[int], cols: Sequence[int], device, packed: bool):
+    """(int64 [S + 1] starts, total) of per-scene [rows_i, cols_i] blocks laid end to end: in elements, or, `packed`, in the uint32
+    words of one bit per element (ceil(cols_i / 32) words per row)"""
+    off = [0]
+    for r, c in zip(rows, cols):
+        off.append(off[-1] + int(r) * ((int(c) + 31) // 32 if packed else int(c)))
+    return torch.tensor(off, dtype=torch.int64, device=device), off[-1]
+
+
+def _sgi_rows(x: torch.Tensor, what: str) -> torch.Tensor:
+    require_cuda(x)
+    if x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise PtcoreError(f"{what}: needs fp32 / bf16 [T, H, D] rows, got {x.dtype} {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def sgi_attn_fwd(q, k, v, cu_q, cu_k, mask=None, mask_row_off=None, scale=None):
+    """-> (out [Tq, H, D], lse [Tq, H] fp32).  Scene i attends rows cu_q[i]:cu_q[i+1] of q to rows cu_k[i]:cu_k[i+1] of k, v; `mask`
+    int32 words, one bit per (query, key) of each scene from word mask_row_off[i], set = masked out, no row fully masked."""
+    q, k, v = _sgi_rows(q, "sgi_attn_fwd"), _sgi_rows(k, "sgi_attn_fwd"), _sgi_rows(v, "sgi_attn_fwd")
+    tq, h, d = q.shape
+    tk = k.shape[0]
+    if k.shape != v.shape or k.shape[1:] != q.shape[1:] or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise PtcoreError(f"sgi_attn_fwd: q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)} {k.dtype}, v {tuple(v.shape)} {v.dtype}")
+    s = cu_q.numel() - 1
+    if cu_k.numel() != s + 1 or cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32:
+        raise PtcoreError("sgi_attn_fwd: cu_q / cu_k must be int32 [S + 1]")
+    scale = float(d) ** -0.5 if scale is None else float(scale)
+    out = torch.empty_like(q)
+    lse = torch.empty((tq, h), dtype=torch.float32, device=q.device)
+    check(lib().ptc_sgi_attn_fwd(ptr(q), ptr(k), ptr(v), dtype_code(q), ptr(cu_q), ptr(cu_k), s, tq, tk, h, d, ptr(mask), ptr(mask_row_off), scale,
+                                 ptr(out), ptr(lse), stream_ptr()), "ptc_sgi_attn_fwd")
+    return out, lse
+
+
+def sgi_attn_bwd(q, k, v, out, dout, lse, cu_q, cu_k, mask=None, mask_row_off=None, scale=None):
+    """(dq, dk, dv) of sgi_attn_fwd; the probabilities are recomputed, the reductions run in a fixed order"""
+    q, k, v = _sgi_rows(q, "sgi_attn_bwd"), _sgi_rows(k, "sgi_attn_bwd"), _sgi_rows(v, "sgi_attn_bwd")
+    tq, h, d = q.shape
+    tk = k.shape[0]
+    s = cu_q.numel() - 1
+    scale = float(d) ** -0.5 if scale is None else float(scale)
+    do = dout.to(q.dtype).contiguous()                  # kept in a name: the copy must outlive the call
+    o = out.contiguous()
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    nbytes = lib().ptc_sgi_attn_workspace_bytes(tq, h)
+    ws = _ws(nbytes, q.device)
+    check(lib().ptc_sgi_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), dtype_code(q), ptr(cu_q), ptr(cu_k), s, tq, tk, h, d, ptr(mask),
+                                 ptr(mask_row_off), scale, ptr(dq), ptr(dk), ptr(dv), ptr(ws), nbytes, stream_ptr()), "ptc_sgi_attn_bwd")
+    return dq, dk, dv
+
+
+def sgi_pack_mask(logits: torch.Tensor, lq: Sequence[int], lk: Sequence[int]):
+    """-> (words int32 [total], row_off int64 [S + 1]).  logits: the [lq_i, lk_i] fp32 mask logits of every scene laid end to end;
+    bit = sigmoid(x) < 0.5, a row whose bits would all be set is cleared (forward_head, :372-378)."""
+    require_cuda(logits)
+    if logits.dtype != torch.float32:
+        raise PtcoreError(f"sgi_pack_mask: fp32 logits, got {logits.dtype}")
+    x = logits.contiguous().reshape(-1)
+    dev = x.device
+    logit_off, total = sgi_offsets(lq, lk, dev, False)
+    if total != x.numel():
+        raise PtcoreError(f"sgi_pack_mask: {x.numel()} logits for blocks of {total}")
+    row_off, nwords = sgi_offsets(lq, lk, dev, True)
+    words = torch.empty(nwords, dtype=torch.int32, device=dev)
+    cu_q, cu_k = sgi_cu(lq, dev), sgi_cu(lk, dev)
+    check(lib().ptc_sgi_pack_mask(ptr(x), ptr(logit_off), ptr(cu_q), ptr(cu_k), len(lq), int(sum(lq)), ptr(row_off), ptr(words), stream_ptr()),
+          "ptc_sgi_pack_mask")
+    return words, row_off
+
+
+def sgi_match_cost(logits: torch.Tensor, cls: torch.Tensor, lq: Sequence[int], lk: Sequence[int], g: Sequence[int], gt_words: torch.Tensor,
+                   gt_word_off: torch.Tensor, gt_cls: torch.Tensor, weights: Sequence[float]):
+    """-> (cost fp32 [sum lq_i g_i], cost_off host list [S + 1]): the Hungarian matcher's cost matrices [lq_i, g_i] of every scene
+    (loss.py:15-52, :331-429) from the flat mask logits, cls [Tq, C] and the packed ground-truth masks [g_i, lk_i]."""
+    require_cuda(logits, cls, gt_words, gt_cls)
+    x = logits.to(torch.float32).contiguous().reshape(-1)
+    c = cls.to(torch.float32).contiguous()
+    dev = x.device
+    logit_off, total = sgi_offsets(lq, lk, dev, False)
+    if total != x.numel() or c.dim() != 2 or c.shape[0] != sum(lq):
+        raise PtcoreError(f"sgi_match_cost: {x.numel()} logits for blocks of {total}, cls {tuple(c.shape)} for {sum(lq)} rows")
+    cost_off, ncost = sgi_offsets(lq, g, dev, False)
+    cost = torch.empty(ncost, dtype=torch.float32, device=dev)
+    cu_q, cu_k, cu_g = sgi_cu(lq, dev), sgi_cu(lk, dev), sgi_cu(g, dev)
+    gc = gt_cls.to(torch.int64).contiguous()
+    if ncost:
+        check(lib().ptc_sgi_match_cost(ptr(x), ptr(logit_off), ptr(c), c.shape[1], ptr(cu_q), ptr(cu_k), ptr(cu_g), len(lq), int(sum(lq)),
+                                       ptr(gt_words), ptr(gt_word_off), ptr(gc), ptr(cost_off), float(weights[0]), float(weights[1]),
+                                       float(weights[2]), ptr(cost), stream_ptr()), "ptc_sgi_match_cost")
+    off, host = 0, [0]
+    for a, b in zip(lq, g):
+        off += int(a) * int(b)
+        host.append(off)
+    return cost, host
+
+
+def sgi_targets(instance, segment, sp_inverse, offset, lk: Sequence[int], g: Sequence[int]):
+    """prepare_target (:517-585) without the [N, G] one-hot -> (sp_size int32 [sum lk], counts int32 [sum g_i lk_i], gt_words int32,
+    word_off int64 [S + 1], inst_cls int64 [sum g_i]); g_i = max instance + 1 of scene i (0: none), lk_i its superpoints."""
+    require_cuda(instance, segment, sp_inverse, offset)
+    dev = instance.device
+    inst = instance.to(torch.int64).contiguous()
+    seg = segment.to(torch.int64).contiguous()
+    spi = sp_inverse.to(torch.int64).contiguous()
+    off = offset.to(torch.int64).contiguous()
+    s, n = off.numel(), inst.numel()
+    if len(lk) != s or len(g) != s:
+        raise PtcoreError("sgi_targets: one superpoint and one instance count per scene")
+    cu_k, cu_g = sgi_cu(lk, dev), sgi_cu(g, dev)
+    cnt_off, ncnt = sgi_offsets(g, lk, dev, False)
+    word_off, nwords = sgi_offsets(g, lk, dev, True)
+    nsp, ninst = int(sum(lk)), int(sum(g))
+    sp_size = torch.empty(nsp, dtype=torch.int32, device=dev)
+    counts = torch.empty(ncnt, dtype=torch.int32, device=dev)
+    words = torch.empty(nwords, dtype=torch.int32, device=dev)
+    inst_cls = torch.empty(ninst, dtype=torch.int64, device=dev)
+    check(lib().ptc_sgi_targets(ptr(inst), ptr(seg), ptr(spi), ptr(off), s, n, ptr(cu_k), ptr(cu_g), ptr(cnt_off), ptr(word_off), nsp, ninst, ncnt,
+                                nwords, ptr(sp_size), ptr(counts), ptr(words), ptr(inst_cls), stream_ptr()), "ptc_sgi_targets")
+    return sp_size, counts, words, word_off, inst_cls

@@ -207,6 +207,19 @@ def indoor_instance_batch(seeds, sizes):
     return collate(scenes)
 
 
+def indoor_superpoint_batch(seeds, sizes, cell: float = 0.5):
+    """indoor_instance_batch plus a `superpoint` id per point: the coarse grid cell of edge `cell` crossed with the instance id,
+    numbered 0.. per scene (an over-segmentation whose pieces never straddle two instances or an instance and the background)"""
+    scenes = [indoor_instance_scene(s, n) for s, n in zip(seeds, sizes)]
+    for sc in scenes:
+        sc.pop("bbox")
+        c = np.floor(sc["coord"] / cell).astype(np.int64)
+        c -= c.min(0)
+        key = ((c[:, 0] * 4096 + c[:, 1]) * 4096 + c[:, 2]) * 4096 + (sc["instance"] + 1)
+        sc["superpoint"] = np.unique(key, return_inverse=True)[1].reshape(-1).astype(np.int64)
+    return collate(scenes)
+
+
 def contrastive_views(seed: int, point_max: int = 102400, grid: float = 0.02, shift=(-1.3, 0.4, -0.2), jitter: float = 0.004):
     """Two views of one indoor scene as ContrastiveViewsGenerator + the MSC config's pipelines leave them
     (configs/scannet/pretrain-msc-v1m1-0-spunet-base.py): each an independent sphere crop of about `point_max` points (the crops
