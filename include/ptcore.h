@@ -844,6 +844,21 @@ int ptc_pg_bias_loss_bwd(const void* bias_pred, int dtype, const float* coord, c
  * ptc_msc_nce_bwd: dfeat1 [n1,c] / dfeat2 [n2,c]: the rows named by match_index are WRITTEN (callers pass zeros) with
  *   d out[0] * dloss[0] (dloss on the device); rows named several times are summed in ascending pair order.
  *   Both use a workspace of ptc_msc_nce_workspace_bytes(p, c) = O(p c).
+ * ptc_msc_csc_nce_fwd: the partitioned InfoNCE of MSC-v1m2 (masked_scene_contrast_v1m2_csc.py:182-252).  A, B as above;
+ *   x1 = coord1 [n1,3] rows match_index[:,0], x2 = coord2 [n2,3] rows match_index[:,1]; the scene of a pair is that of its view-1
+ *   row under offset1 [nb] int32 (1 <= nb <= 32766).  match_index may be in any order: the pairs are grouped by scene on the device
+ *   (stable sort) and a pair with an index outside its matrix or beyond offset1[nb-1] is dropped.  Logit (i, j), same scene, has the
+ *   class of rel = x1[j] - x2[i], d = sqrt(rel.x^2 + rel.y^2 + rel.z^2 + 1e-7) (fp32, unfused): 0 / 1: r1 < d <= r2 and rel.z > 0 /
+ *   < 0;  2 / 3: d > r2 and rel.z > 0 / < 0;  4: the rest.  lse_c[i] = log(exp(S_ii / t) + sum over j != i of class c of
+ *   exp(S_ij / t)); a class is present in a scene when any element of its P_b x P_b class matrix has it (diagonal included).
+ *   out [3] = (sum_b sum_{c present} mean_{i in b}(lse_c[i] - S_ii / t) / (nb partitions),  run_last / nb,
+ *   sum_b (mean(S_b) - run_b / P_b) / nb) with run_b the running sum of mean(diag S_b) over the non-empty scenes in ascending order.
+ *   counts [nb,5] int64: the members of each class in each scene.  No host read.  Saved for the backward, all in scene order:
+ *   an, bn [p,c], na, nbn [p], xs1, xs2 [p,4] (coordinates and the scene), smatch [p,2] int64, start [nb+2] int32, and per row and
+ *   class rmax [p,5] = the largest logit (diagonal included) and rinv [p,5] = 1 / sum exp(z - rmax) (0 for a class absent from the
+ *   row's scene), roww [p] = 1 / (nb partitions P_b).  lse [p,5] = rmax - log(rinv) (+inf for an absent class) is written as well.
+ * ptc_msc_csc_nce_bwd: dfeat1 / dfeat2 as ptc_msc_nce_bwd (rows WRITTEN; repeated rows summed in ascending scene-order position).
+ *   Both use a workspace of ptc_msc_csc_nce_workspace_bytes(p, c, nb) = O(p c + nb); r1 <= r2 is required.
  * ------------------------------------------------------------------------------------------ */
 size_t ptc_msc_match_workspace_bytes(int64_t n);
 int ptc_msc_match(const float* xyz, const int32_t* offset, const float* new_xyz, const int32_t* new_offset, int b, int64_t n, int64_t m,
@@ -864,6 +879,16 @@ int ptc_msc_nce_fwd(const float* feat1, int64_t n1, const float* feat2, int64_t 
 int ptc_msc_nce_bwd(const float* an, const float* bn, const float* na, const float* nb, const float* lse, const int64_t* match_index,
                     int64_t p, int c, int64_t n1, int64_t n2, float nce_t, const float* dloss, float* dfeat1, float* dfeat2,
                     void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+size_t ptc_msc_csc_nce_workspace_bytes(int64_t p, int c, int nb);
+int ptc_msc_csc_nce_fwd(const float* feat1, int64_t n1, const float* feat2, int64_t n2, const float* coord1, const float* coord2,
+                        const int32_t* offset1, int nb, const int64_t* match_index, int64_t p, int c, float nce_t, float r1, float r2,
+                        int partitions, float* an, float* bn, float* na, float* nbn, float* xs1, float* xs2, int64_t* smatch,
+                        int32_t* start, float* lse, float* rmax, float* rinv, float* roww, int64_t* counts, float* out, void* workspace,
+                        size_t workspace_bytes, ptc_stream_t stream);
+int ptc_msc_csc_nce_bwd(const float* an, const float* bn, const float* na, const float* nbn, const float* xs1, const float* xs2,
+                        const int64_t* smatch, const int32_t* start, const float* rmax, const float* rinv, const float* roww, int64_t p, int c, int nb,
+                        int64_t n1, int64_t n2, float nce_t, float r1, float r2, const float* dloss, float* dfeat1, float* dfeat2,
+                        void* workspace, size_t workspace_bytes, ptc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Context-aware classifier (csrc/cac.hip; pointcept/models/context_aware_classifier/context_aware_classifier_v1m1_base.py).

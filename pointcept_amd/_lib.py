@@ -171,6 +171,11 @@ _SIGNATURES = {
                                 c_size, c_ptr]),
     "ptc_msc_nce_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_i64, c_i64, c_f32, c_ptr, c_ptr, c_ptr, c_ptr,
                                 c_size, c_ptr]),
+    "ptc_msc_csc_nce_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
+    "ptc_msc_csc_nce_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_int, c_f32, c_f32, c_f32, c_int]
+                            + [c_ptr] * 14 + [c_ptr, c_size, c_ptr]),
+    "ptc_msc_csc_nce_bwd": (c_int, [c_ptr] * 11 + [c_i64, c_int, c_int, c_i64, c_i64, c_f32, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr,
+                                                    c_size, c_ptr]),
     "ptc_cac_supported": (c_int, [c_int, c_int]),
     "ptc_cac_pool_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
     "ptc_cac_pool_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size,

@@ -36,7 +36,8 @@ settings), and so a regression can be bisected without a rebuild.
                      cross-check of csrc/pg_cluster.hip)
   PTC_MSC=0          Masked Scene Contrast's cross masks, view matching, pair selection and InfoNCE loss (masked_scene_contrast.py) run
                      as the reference's own expression on ops.knn_query and torch -- voxel_grid + unique, brute-force kNN + radius
-                     filter, the dense P x P similarity matrix -- instead of csrc/msc.hip (A/B baseline, and the CPU path of the port)
+                     filter, the dense P x P similarity matrix; for MSC-v1m2 the per-scene loop with its dense partition matrices and
+                     one masked CrossEntropy per class -- instead of csrc/msc.hip (A/B baseline, and the CPU path of the port)
   PTC_CAC=0          the context-aware classifier's prototype pooling, cosine classifier and distillation loss
                      (context_aware_classifier.py) run as the reference's own expression -- per-class and per-scene loops, dense
                      softmax / one-hot temporaries, library GEMMs -- instead of csrc/cac.hip (A/B baseline, and the CPU path of the port)

@@ -1403,6 +1403,80 @@ def msc_nce_torch(feat1, feat2, match_index, nce_t: float):
     return loss, pos_sim, neg_sim
 
 
+class _MSCCscNce(Function):
+    @staticmethod
+    def forward(ctx, feat1, coord1, offset1, feat2, coord2, match_index, nce_t, r1, r2, partitions):
+        out, _, state = ops.msc_csc_nce_fwd(feat1, coord1, offset1, feat2, coord2, match_index, nce_t, r1, r2, partitions)
+        ctx.save_for_backward(*state)
+        ctx.shape = (feat1.shape[0], feat2.shape[0], float(nce_t), float(r1), float(r2))
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, g_loss, g_pos, g_neg):
+        n1, n2, nce_t, r1, r2 = ctx.shape
+        if g_loss is None:
+            return (None,) * 10
+        d1, d2 = ops.msc_csc_nce_bwd(tuple(ctx.saved_tensors), n1, n2, nce_t, r1, r2, g_loss)
+        return d1, None, None, d2, None, None, None, None, None, None
+
+
+def msc_csc_nce(feat1, coord1, offset1, feat2, coord2, match_index, nce_t: float, r1: float, r2: float, partitions: int = 4):
+    """(nce loss, pos_sim, neg_sim) of MSC-v1m2's compute_contrastive_loss (masked_scene_contrast_v1m2_csc.py:212-254) on the fused
+    kernels: one InfoNCE per scene and partition class of rel = x1[j] - x2[i], summed over the classes present in the scene and
+    divided by (scenes * partitions).  match_index in any row order; no P_b x P_b tensor and no host read.  fp32 scalars, the loss
+    differentiable in feat1 / feat2, the two similarities detached; 16-bit features are cast up (enable_amp = False in the recipe)."""
+    with torch.autocast(device_type=feat1.device.type, enabled=False):
+        loss, pos, neg = _MSCCscNce.apply(feat1.float(), coord1.float(), offset1, feat2.float(), coord2.float(), match_index, float(nce_t),
+                                          float(r1), float(r2), int(partitions))
+    return loss, pos.detach(), neg.detach()
+
+
+def msc_csc_partitions(coord1, coord2, r1: float, r2: float):
+    """compute_partitions (:182-200) on fp32 coordinates: [len(coord2), len(coord1)] classes 0..3 and -1e7 for the rest; element
+    (i, j) is the class of coord1[j] - coord2[i]"""
+    coord1, coord2 = coord1.float(), coord2.float()
+    rel = coord1.unsqueeze(0) - coord2.unsqueeze(1)
+    up, down = rel[:, :, 2] > 0.0, rel[:, :, 2] < 0.0
+    dist = torch.sqrt(torch.sum(rel.pow(2), 2).add(1e-7))
+    part = torch.full(dist.shape, -1e7, device=coord1.device)
+    mid, far = (dist > r1) & (dist <= r2), dist > r2
+    part[mid & up] = 0
+    part[mid & down] = 1
+    part[far & up] = 2
+    part[far & down] = 3
+    return part
+
+
+def msc_csc_nce_torch(feat1, coord1, offset1, feat2, coord2, match_index, nce_t: float, r1: float, r2: float, partitions: int = 4):
+    """the reference's expression (:212-254): a host loop over the scenes that hold pairs, the dense P_b x P_b similarity and
+    partition matrices, one masked CrossEntropy per class present (A/B and CPU path).  The partitions always come from
+    coord.float(), so a float64 run of the features sees the classes of the fp32 run."""
+    from .structure import offset2batch
+
+    a = feat1[match_index[:, 0]]
+    b = feat2[match_index[:, 1]]
+    a = a / (torch.norm(a, p=2, dim=1, keepdim=True) + 1e-7)
+    b = b / (torch.norm(b, p=2, dim=1, keepdim=True) + 1e-7)
+    x1, x2 = coord1[match_index[:, 0]], coord2[match_index[:, 1]]
+    loss = torch.zeros((), dtype=a.dtype, device=a.device)
+    pos_sim, neg_sim = torch.zeros_like(loss), torch.zeros_like(loss)
+    batch = offset2batch(offset1)[match_index[:, 0]]
+    for batch_id in batch.unique():
+        sel = batch == batch_id
+        sim = torch.mm(a[sel], b[sel].transpose(1, 0))
+        with torch.no_grad():
+            pos_sim += torch.diagonal(sim).mean()
+            neg_sim += sim.mean(dim=-1).mean() - pos_sim / sel.sum()
+        labels = torch.arange(sim.shape[0], device=a.device).long()
+        part = msc_csc_partitions(x1[sel], x2[sel], r1, r2)
+        for part_id in part.unique():
+            keep = part == part_id
+            keep.fill_diagonal_(True)
+            loss = loss + torch.nn.functional.cross_entropy(torch.div(sim, nce_t) - 1e9 * (~keep).to(sim.dtype), labels, reduction="mean")
+    n_scenes = len(offset1)
+    return loss / (n_scenes * partitions), pos_sim / n_scenes, neg_sim / n_scenes
+
+
 def msc_candidates_torch(k: int, max_radius: float, xyz, offset, new_xyz, new_offset):
     """(count, cand) of ops.msc_match written as the reference writes it: knn_query, then `distance < max_radius` (:147-162)"""
     idx, dist = ops.knn_query(k, xyz.float(), offset.int(), new_xyz.float(), new_offset.int())

@@ -12,7 +12,14 @@ forward(data_dict) keys and result-dict keys.  Registered only when named: compa
 * The four random draws go through `draw(kind, ...)`: randperm(patch_num), randint(count.max(), count.shape), randperm(P) and
   random.random(), each made as the reference makes it, in its order, on its device; tests replay recorded draws through it.
 * PTC_MSC=0: the reference's own expression written on ops.knn_query and torch (A/B baseline; the CPU path of the port).
-MSC-v1m2 (the CSC partitions) and the PointContrast config variant are not ported.
+
+MSC-v1m2 (masked_scene_contrast_v1m2_csc.py, configs/scannet/pretrain-msc-v1m2-0-spunet-csc.py: the ScanNet-Pair / PointContrast
+recipe with mask_rate = 0 and no reconstruction heads) is MaskedSceneContrastCSC: the same masks, matching, backbone and forward;
+only compute_contrastive_loss differs.  It takes the two origin coordinates and computes, per scene, one InfoNCE per partition class
+of rel = x1[j] - x2[i] (distance bands r1 / r2, above / below): functional.msc_csc_nce -- pairs grouped by scene on the device, the
+class of a logit computed in the tile from staged coordinates, five online log-sum-exps per row, no P_b x P_b tensor and no host
+read (the reference reads 1 + scenes times).  PTC_MSC=0: functional.msc_csc_nce_torch, the reference's loop.  The ScanNet-Pair
+dataset class and the PointContrast data pipeline stay the reference's.
 """
 from __future__ import annotations
 
@@ -145,6 +152,10 @@ class MaskedSceneContrast(nn.Module):
             dist.all_reduce(neg_sim)
         return loss / world, pos_sim / world, neg_sim / world
 
+    def _contrast(self, view1_feat, view1_origin_coord, view1_offset, view2_feat, view2_origin_coord, view2_offset, match_index):
+        """forward's call of compute_contrastive_loss; v1m2 passes the origin coordinates as well"""
+        return self.compute_contrastive_loss(view1_feat, view1_offset, view2_feat, view2_offset, match_index)
+
     # ---- :205-310 ----
     def forward(self, data_dict):
         view1_origin_coord = data_dict["view1_origin_coord"]
@@ -182,7 +193,8 @@ class MaskedSceneContrast(nn.Module):
         match_index = self.match_contrastive_pair(view1_origin_coord, view1_offset, view2_origin_coord, view2_offset,
                                                   max_k=self.matching_max_k, max_radius=self.matching_max_radius)
         self.last = dict(view1_point_mask=view1_point_mask, view2_point_mask=view2_point_mask, match_index=match_index)
-        nce_loss, pos_sim, neg_sim = self.compute_contrastive_loss(view1_feat, view1_offset, view2_feat, view2_offset, match_index)
+        nce_loss, pos_sim, neg_sim = self._contrast(view1_feat, view1_origin_coord, view1_offset, view2_feat, view2_origin_coord,
+                                                    view2_offset, match_index)
         loss = nce_loss * self.contrast_weight
         result_dict = dict(nce_loss=nce_loss, pos_sim=pos_sim, neg_sim=neg_sim)
 
@@ -212,3 +224,34 @@ class MaskedSceneContrast(nn.Module):
 
         result_dict["loss"] = loss
         return result_dict
+
+
+class MaskedSceneContrastCSC(MaskedSceneContrast):
+    """MSC-v1m2 (masked_scene_contrast_v1m2_csc.py:24-377): MSC-v1m1 with the contrastive loss split into CSC partitions"""
+
+    def __init__(self, backbone, backbone_in_channels, backbone_out_channels, mask_grid_size=0.1, mask_rate=0.4, view1_mix_prob=0,
+                 view2_mix_prob=0, matching_max_k=8, matching_max_radius=0.03, matching_max_pair=8192, nce_t=0.4, contrast_weight=1,
+                 reconstruct_weight=1, reconstruct_color=True, reconstruct_normal=True, partitions=4, r1=0.125, r2=2):
+        super().__init__(backbone, backbone_in_channels, backbone_out_channels, mask_grid_size, mask_rate, view1_mix_prob, view2_mix_prob,
+                         matching_max_k, matching_max_radius, matching_max_pair, nce_t, contrast_weight, reconstruct_weight,
+                         reconstruct_color, reconstruct_normal)
+        self.partitions = partitions
+        self.r1 = r1
+        self.r2 = r2
+
+    # ---- :202-264 ----
+    def compute_contrastive_loss(self, view1_feat, view1_coord, view1_offset, view2_feat, view2_coord, view2_offset, match_index):
+        assert view1_offset.shape == view2_offset.shape
+        fn = PF.msc_csc_nce if self._kernels(view1_feat) else PF.msc_csc_nce_torch
+        loss, pos_sim, neg_sim = fn(view1_feat, view1_coord, view1_offset, view2_feat, view2_coord, match_index, self.nce_t, self.r1,
+                                    self.r2, self.partitions)
+        world = _world_size()
+        if world > 1:
+            dist.all_reduce(loss)
+            dist.all_reduce(pos_sim)
+            dist.all_reduce(neg_sim)
+        return loss / world, pos_sim / world, neg_sim / world
+
+    def _contrast(self, view1_feat, view1_origin_coord, view1_offset, view2_feat, view2_origin_coord, view2_offset, match_index):
+        return self.compute_contrastive_loss(view1_feat, view1_origin_coord, view1_offset, view2_feat, view2_origin_coord, view2_offset,
+                                             match_index)

@@ -1854,6 +1854,68 @@ def msc_nce_bwd(state, n1: int, n2: int, nce_t: float, dloss: torch.Tensor):
     return d1, d2
 
 
+def _msc_csc_nce_args(feat1, coord1, offset1, feat2, coord2, match_index, r1, r2):
+    require_cuda(feat1, coord1, offset1, feat2, coord2, match_index)
+    if feat1.dtype != torch.float32 or feat2.dtype != torch.float32 or feat1.dim() != 2 or feat2.dim() != 2 or feat1.shape[1] != feat2.shape[1]:
+        raise PtcoreError("msc_csc_nce: feat1 / feat2 must be fp32 [N, C] with equal C")
+    c = feat1.shape[1]
+    if c % 4 or not 4 <= c <= 256:
+        raise PtcoreError(f"msc_csc_nce: C={c} is not a multiple of 4 in [4, 256]")
+    mi = match_index.to(torch.int64).contiguous()
+    if mi.dim() != 2 or mi.shape[1] != 2 or mi.shape[0] < 1:
+        raise PtcoreError("msc_csc_nce: match_index must be [P, 2] with P >= 1")
+    x1, x2 = _xyz(coord1, "msc_csc_nce: coord1"), _xyz(coord2, "msc_csc_nce: coord2")
+    if x1.shape[0] != feat1.shape[0] or x2.shape[0] != feat2.shape[0]:
+        raise PtcoreError("msc_csc_nce: one coordinate row per feature row")
+    off = offset1.to(torch.int32).contiguous()
+    if off.dim() != 1 or off.numel() < 1:
+        raise PtcoreError("msc_csc_nce: offset1 must list at least one scene")
+    if not float(r1) <= float(r2):
+        raise PtcoreError(f"msc_csc_nce: needs r1 <= r2, got r1={r1} r2={r2}")
+    return feat1.contiguous(), x1, off, feat2.contiguous(), x2, mi, c
+
+
+def msc_csc_nce_fwd(feat1, coord1, offset1, feat2, coord2, match_index, nce_t: float, r1: float, r2: float, partitions: int = 4):
+    """-> (out [3] fp32 = (nce loss, pos_sim, neg_sim) of masked_scene_contrast_v1m2_csc.py:212-254, counts [nB, 5] int64 = the members
+    of each partition class per scene, state for msc_csc_nce_bwd).  match_index in any order; no P x P matrix and no host read"""
+    f1, x1, off, f2, x2, mi, c = _msc_csc_nce_args(feat1, coord1, offset1, feat2, coord2, match_index, r1, r2)
+    p, nb, dev = mi.shape[0], off.numel(), f1.device
+    an = torch.empty((p, c), dtype=torch.float32, device=dev)
+    bn = torch.empty((p, c), dtype=torch.float32, device=dev)
+    vec = torch.empty((3, p), dtype=torch.float32, device=dev)        # |a|, |b|, 1 / (nB partitions P_b)
+    xs = torch.empty((2, p, 4), dtype=torch.float32, device=dev)      # (x1, scene), (x2, scene) in scene order
+    smi = torch.empty((p, 2), dtype=torch.int64, device=dev)
+    start = torch.empty(nb + 2, dtype=torch.int32, device=dev)
+    lse = torch.empty((3, p, 5), dtype=torch.float32, device=dev)     # lse, row max, 1 / row sum, per class
+    counts = torch.empty((nb, 5), dtype=torch.int64, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    nbytes = lib().ptc_msc_csc_nce_workspace_bytes(p, c, nb)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_msc_csc_nce_fwd(ptr(f1), f1.shape[0], ptr(f2), f2.shape[0], ptr(x1), ptr(x2), ptr(off), nb, ptr(mi), p, c, float(nce_t),
+                                    float(r1), float(r2), int(partitions), ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(xs[0]), ptr(xs[1]),
+                                    ptr(smi), ptr(start), ptr(lse[0]), ptr(lse[1]), ptr(lse[2]), ptr(vec[2]), ptr(counts), ptr(out), ptr(ws), nbytes, stream_ptr()),
+          "ptc_msc_csc_nce_fwd")
+    return out, counts, (an, bn, vec, xs, smi, start, lse)
+
+
+def msc_csc_nce_bwd(state, n1: int, n2: int, nce_t: float, r1: float, r2: float, dloss: torch.Tensor):
+    """(dfeat1 [n1, C], dfeat2 [n2, C]) fp32 from the forward's state and d loss (a device scalar: no host read)"""
+    an, bn, vec, xs, smi, start, lse = state
+    p, c = an.shape
+    nb, dev = start.numel() - 2, an.device
+    if not float(r1) <= float(r2):
+        raise PtcoreError(f"msc_csc_nce: needs r1 <= r2, got r1={r1} r2={r2}")
+    d1 = torch.zeros((int(n1), c), dtype=torch.float32, device=dev)
+    d2 = torch.zeros((int(n2), c), dtype=torch.float32, device=dev)
+    g = dloss.to(torch.float32).reshape(1).contiguous()
+    nbytes = lib().ptc_msc_csc_nce_workspace_bytes(p, c, nb)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_msc_csc_nce_bwd(ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(xs[0]), ptr(xs[1]), ptr(smi), ptr(start), ptr(lse[1]),
+                                    ptr(lse[2]), ptr(vec[2]), p, c, nb, int(n1), int(n2), float(nce_t), float(r1), float(r2), ptr(g), ptr(d1), ptr(d2),
+                                    ptr(ws), nbytes, stream_ptr()), "ptc_msc_csc_nce_bwd")
+    return d1, d2
+
+
 # ------------------------------------------------------------------------------------------------
 # context-aware classifier (csrc/cac.hip): prototype pooling, segmented cosine classifier, distillation loss
 # ------------------------------------------------------------------------------------------------
