@@ -966,6 +966,38 @@ int ptc_sgi_targets(const int64_t* instance, const int64_t* segment, const int64
                     int64_t total_inst, int64_t total_counts, int64_t total_words, int32_t* sp_size, int32_t* counts, uint32_t* gt_words,
                     int64_t* inst_cls, ptc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sonata-v1m1 distillation loss (csrc/sonata.hip; pointcept/models/sonata/sonata_v1m1_base.py:267-291, :443-454).
+ * teacher [nt,k] / student [ns,k] logits in fp32, fp16 or bf16 (ptc_dtype tags; converted in the load, fp32 arithmetic), k a
+ * multiple of 64 up to 8192 (see the _supported entry); match_index [m,2] int64 = (student row, teacher row), listed by ascending
+ * scene; a pair with a row outside its tensor contributes nothing.  With e_ik = exp(teacher[match_index[i,1]][k] / temp) the
+ * Sinkhorn-Knopp matrix is e_ik a_k b_i and is never stored.  max_groups caps the workgroups of a launch (0 = the default); a pass
+ * that sums columns writes one partial row per workgroup into partials [the _groups entry's count, k] and sums them in index order:
+ * no atomics, bit-reproducible.  m = 0 launches nothing and writes nothing.
+ * Column sums: r [k] = sum_i e_ik b_i (b [m] or NULL = 1).
+ * Row pass: from a [k], c [m] = sum_k e_ik a_k and b [m] = 1 / (n c); with partials != NULL also r [k] = sum_i e_ik b_i of the new b.
+ * Distillation forward: c as above, target_ik = e_ik a_k / c_i, lse [m] = logsumexp_k of the student row over student_temp,
+ *   row_loss [m] = lse_i - sum_k target_ik s_ik / student_temp, scene_mean [num_scenes] = the mean of row_loss over the pairs of each
+ *   scene student_batch[student row] (0 without pairs), loss [1] = the mean of scene_mean over the scenes up to the last matched one
+ *   (torch_scatter.segment_coo without dim_size), roww [m] = 1 / (pairs of the scene x those scenes).  num_scenes bounds the scene ids.
+ * Distillation backward: dpred [ns,k] (the student's dtype) row match_index[i,0] = dloss[0] roww_i / student_temp
+ *   (softmax(s_i / student_temp) - target_i), each matched row WRITTEN once (they are unique); the caller zeroes the rest.
+ * ------------------------------------------------------------------------------------------ */
+int ptc_sonata_supported(int k);
+int64_t ptc_sonata_groups(int64_t m, int k, int max_groups);
+int ptc_sonata_colsum(const void* teacher, int tdtype, int64_t nt, const int64_t* match_index, int64_t m, int k, double temp,
+                      const float* b, int max_groups, float* partials, float* r, ptc_stream_t stream);
+int ptc_sonata_rowpass(const void* teacher, int tdtype, int64_t nt, const int64_t* match_index, int64_t m, int k, double temp,
+                       const float* a, double n, float* c, float* b, int max_groups, float* partials, float* r, ptc_stream_t stream);
+int ptc_sonata_distill_fwd(const void* teacher, int tdtype, int64_t nt, const void* student, int sdtype, int64_t ns,
+                           const int64_t* match_index, const int64_t* student_batch, int num_scenes, int64_t m, int k, double temp,
+                           double student_temp, const float* a, int max_groups, float* c, float* lse, float* row_loss, float* roww,
+                           float* scene_mean, float* loss, ptc_stream_t stream);
+int ptc_sonata_distill_bwd(const void* teacher, int tdtype, int64_t nt, const void* student, int sdtype, int64_t ns,
+                           const int64_t* match_index, int64_t m, int k, double temp, double student_temp, const float* a,
+                           const float* c, const float* lse, const float* roww, const float* dloss, int max_groups, void* dpred,
+                           ptc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,7 @@ HIP_SOURCES = [
     "msc.hip",
     "cac.hip",
     "sgiformer.hip",
+    "sonata.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

@@ -82,6 +82,7 @@ OPT_IN_MODEL_CLASSES = {
     "MSC-v1m2": ("masked_scene_contrast", "MaskedSceneContrastCSC"),  # masked_scene_contrast_v1m2_csc.py:24
     "CAC-v1m1": ("context_aware_classifier", "CACSegmentor"),         # context_aware_classifier_v1m1_base.py:17
     "SGIFormer-v1m1": ("sgiformer", "SGIFormer"),                      # sgiformer/sgiformer_v1m1_base.py:482
+    "Sonata-v1m1": ("sonata", "Sonata"),                              # sonata/sonata_v1m1_base.py:71
 }
 
 
@@ -108,7 +109,7 @@ def register_models(registry, names=None, force: bool = True) -> list:
     """Registers the engine's module-level ports in the reference's `MODELS` registry (pointcept/models/builder.py) under the
     names the reference's configs use, replacing the CUDA-library implementations (`force=True`), so that
     `MODELS.build(cfg.model.backbone)` constructs them.  Returns the names registered.  Without `names`: every name of
-    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs, PointGroup, MSC-v1m1 / -v1m2, CAC, SGIFormer) only when named.
+    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs, PointGroup, MSC-v1m1 / -v1m2, CAC, SGIFormer, Sonata) only when named.
 
         from pointcept.models.builder import MODELS
         import pointcept_amd.compat; pointcept_amd.compat.register_models(MODELS)

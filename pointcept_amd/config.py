@@ -44,6 +44,10 @@ settings), and so a regression can be bisected without a rebuild.
   PTC_SGI=0          SGIFormer's decoder attention, attention-mask packing, matcher cost and target builder (sgiformer.py) run as the
                      reference's own expression -- a Python loop over scenes, dense [heads, Lq, Lk] probabilities, [Lq, M] BCE maps,
                      an [N, instances] one-hot -- instead of csrc/sgiformer.hip (A/B baseline, and the CPU path of the port)
+  PTC_SONATA=0       Sonata's distillation loss (sonata.py, functional.sonata_distill) runs as the reference's own expression -- the
+                     gathered teacher rows, exp and three Sinkhorn-Knopp iterations over a dense M x K fp32 matrix, log_softmax of the
+                     gathered student rows and their product -- instead of the scaling-vector passes of csrc/sonata.hip (A/B baseline,
+                     and the CPU path of the port); view matching and the masks run as knn_query + radius filter and torch.unique
   PTC_FUSE_BLOCK=0   the three residual joints of a PTv3 Block run as separate LayerNorm / add / cast
                      kernels instead of the fused add_norm passes
 """
@@ -73,6 +77,7 @@ PG_CLUSTER = _flag("PTC_PG_CLUSTER", True)
 MSC_KERNELS = _flag("PTC_MSC", True)
 CAC_KERNELS = _flag("PTC_CAC", True)
 SGI_KERNELS = _flag("PTC_SGI", True)
+SONATA_KERNELS = _flag("PTC_SONATA", True)
 WGRAD_BLK = _flag("PTC_WGRAD_BLK", True)
 FUSE_BN_TAIL = _flag("PTC_FUSE_BN_TAIL", True)
 BATCH_BN_COUNTERS = _flag("PTC_BATCH_BN_COUNTERS", True)

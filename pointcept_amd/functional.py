@@ -1912,3 +1912,118 @@ def sgi_targets_torch(instance, segment, sp_inverse, offset) -> SGITargets:
         masks.append(inst_sp_mask_)
         cls.append(inst_cls_)
     return SGITargets(counts, SGIPacked.from_bool(masks), cls)
+
+
+# ------------------------------------------------------------------------------------------------
+# Sonata-v1m1 (sonata_v1m1_base.py:267-291, :443-454): Sinkhorn-Knopp targets from the teacher and the soft cross entropy of the
+# student against them, reduced to the mean over scenes of the per-scene means.  csrc/sonata.hip keeps the Sinkhorn matrix as two
+# scaling vectors (e_ik a_k b_i) and never stores anything of size M x K; sonata_distill_torch is the reference's expression, used
+# for CPU tensors, for prototype counts the kernels refuse and under PTC_SONATA=0 (config.SONATA_KERNELS).
+# ------------------------------------------------------------------------------------------------
+def _sonata_use_kernels(teacher_sim, student_sim, num_iter, use_kernels) -> bool:
+    if use_kernels is None:
+        use_kernels = config.SONATA_KERNELS and teacher_sim.is_cuda
+    return bool(use_kernels and num_iter >= 1 and teacher_sim.dtype != torch.float64 and student_sim.dtype != torch.float64
+                and teacher_sim.dim() == 2 and ops.sonata_supported(teacher_sim.shape[1]))
+
+
+def sonata_sinkhorn_scales(teacher_sim, match_index, teacher_temp: float, num_iter: int = 3, all_reduce=None, max_groups: int = 0):
+    """The prototype scales a [K] after num_iter Sinkhorn-Knopp iterations over e_ik = exp(teacher_sim[match_index[i, 1]] / temp):
+    the assignment of :267-291 is e_ik a_k / sum_k e_ik a_k.  num_iter passes over the teacher rows (the last row normalisation is
+    left to the loss pass).  all_reduce(tensor) sums a tensor over the ranks in place: it is called on the row count and on every
+    K-vector of column sums."""
+    m, k = match_index.shape[0], teacher_sim.shape[1]
+    n = float(m)
+    if all_reduce is not None:
+        cnt = torch.tensor([m], dtype=torch.float64, device=teacher_sim.device)
+        all_reduce(cnt)
+        n = float(cnt.item())
+    r = ops.sonata_colsum(teacher_sim, match_index, teacher_temp, None, max_groups)
+    for it in range(num_iter):
+        if all_reduce is not None:
+            all_reduce(r)
+        a = torch.reciprocal(r * float(k))
+        if it + 1 < num_iter:
+            _, _, r = ops.sonata_rowpass(teacher_sim, match_index, teacher_temp, a, n, True, max_groups)
+    return a
+
+
+class _SonataDistill(Function):
+    @staticmethod
+    def forward(ctx, student_sim, teacher_sim, match_index, student_batch, num_scenes, teacher_temp, student_temp, num_iter, all_reduce,
+                max_groups):
+        a = sonata_sinkhorn_scales(teacher_sim, match_index, teacher_temp, num_iter, all_reduce, max_groups)
+        loss, _, state = ops.sonata_distill_fwd(teacher_sim, student_sim, match_index, student_batch, num_scenes, teacher_temp, student_temp, a,
+                                                max_groups)
+        ctx.save_for_backward(*state)
+        ctx.args = (float(teacher_temp), float(student_temp), int(max_groups))
+        return loss[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss):
+        tt, st, cap = ctx.args
+        return (ops.sonata_distill_bwd(tuple(ctx.saved_tensors), tt, st, dloss, cap),) + (None,) * 9
+
+
+def sonata_distill(teacher_sim, student_sim, match_index, student_batch, teacher_temp: float, student_temp: float, num_iter: int = 3,
+                   all_reduce=None, num_scenes: Optional[int] = None, max_groups: int = 0, use_kernels=None):
+    """mean over scenes of the per-scene mean of -sum_k sinkhorn_knopp(teacher_sim[match_index[:, 1]], teacher_temp)_k
+    log_softmax(student_sim[match_index[:, 0]] / student_temp)_k (:437-454): an fp32 scalar, differentiable in student_sim (the
+    gradient has student_sim's dtype; unmatched rows are exactly zero), the teacher detached.  The scene of a pair is
+    student_batch[match_index[:, 0]] and must ascend along match_index, as segment_coo requires; the divisor is the scene of the last
+    pair + 1.  num_scenes bounds student_batch (default: read from its last element, one host read).  all_reduce: see
+    sonata_sinkhorn_scales.  Logits in fp32, bf16 or fp16 are read as they are; all arithmetic is fp32."""
+    if not _sonata_use_kernels(teacher_sim, student_sim, num_iter, use_kernels):
+        return sonata_distill_torch(teacher_sim, student_sim, match_index, student_batch, teacher_temp, student_temp, num_iter, all_reduce)
+    if match_index.shape[0] == 0:
+        # no kernel to launch: the reference's mean over no rows (NaN) with an all-zero gradient; the other ranks still get this
+        # rank's (zero) share of their column sums
+        if all_reduce is not None:
+            sonata_sinkhorn_scales(teacher_sim, match_index, teacher_temp, num_iter, all_reduce, max_groups)
+        return student_sim[match_index[:, 0]].float().mean()
+    if num_scenes is None:
+        num_scenes = int(student_batch[-1]) + 1
+    with torch.autocast(device_type=student_sim.device.type, enabled=False):
+        return _SonataDistill.apply(student_sim, teacher_sim.detach(), match_index, student_batch, int(num_scenes), float(teacher_temp),
+                                    float(student_temp), int(num_iter), all_reduce, int(max_groups))
+
+
+def sonata_sinkhorn_torch(feat, temp: float, num_iter: int = 3, all_reduce=None):
+    """sinkhorn_knopp (:267-291) on the gathered teacher rows feat [M, K]: fp32 (float64 input stays float64)"""
+    feat = feat if feat.dtype == torch.float64 else feat.float()
+    q = torch.exp(feat / temp).t()
+    k = q.shape[0]
+    n = q.shape[1]
+    if all_reduce is not None:
+        cnt = torch.tensor([n], dtype=torch.float64, device=feat.device)
+        all_reduce(cnt)
+        n = float(cnt.item())
+    sum_q = q.sum()
+    if all_reduce is not None:
+        all_reduce(sum_q)
+    q = q / sum_q
+    for _ in range(num_iter):
+        q_row_sum = q.sum(dim=1, keepdim=True)
+        if all_reduce is not None:
+            all_reduce(q_row_sum)
+        q = q / q_row_sum / k
+        q = q / q.sum(dim=0, keepdim=True) / n
+    q = q * n
+    return q.t()
+
+
+def sonata_distill_torch(teacher_sim, student_sim, match_index, student_batch, teacher_temp: float, student_temp: float, num_iter: int = 3,
+                         all_reduce=None):
+    """the reference's expression (:437-454): the dense Sinkhorn matrix, log_softmax of the gathered student rows, their product,
+    and segment_coo(reduce="mean") without dim_size followed by .mean()"""
+    with torch.no_grad():
+        target = sonata_sinkhorn_torch(teacher_sim.detach()[match_index[:, 1]], teacher_temp, num_iter, all_reduce)
+    loss = -torch.sum(target * F.log_softmax(student_sim[match_index[:, 0]] / student_temp, dim=-1), dim=-1)
+    if loss.shape[0] == 0:
+        return loss.mean()
+    index = student_batch[match_index[:, 0]].long()
+    scenes = int(index[-1]) + 1
+    total = torch.zeros(scenes, dtype=loss.dtype, device=loss.device).index_add(0, index, loss)
+    count = torch.bincount(index, minlength=scenes).clamp(min=1)
+    return (total / count).mean()

@@ -2174,3 +2174,126 @@ def sgi_targets(instance, segment, sp_inverse, offset, lk: Sequence[int], g: Seq
     check(lib().ptc_sgi_targets(ptr(inst), ptr(seg), ptr(spi), ptr(off), s, n, ptr(cu_k), ptr(cu_g), ptr(cnt_off), ptr(word_off), nsp, ninst, ncnt,
                                 nwords, ptr(sp_size), ptr(counts), ptr(words), ptr(inst_cls), stream_ptr()), "ptc_sgi_targets")
     return sp_size, counts, words, word_off, inst_cls
+
+
+# ------------------------------------------------------------------------------------------------
+# Sonata-v1m1 distillation loss (csrc/sonata.hip): Sinkhorn-Knopp in scaling-vector form and the fused soft cross entropy
+# ------------------------------------------------------------------------------------------------
+def sonata_supported(k: int) -> bool:
+    """the kernels take K prototypes, a multiple of 64 up to 8192"""
+    return bool(lib().ptc_sonata_supported(int(k)))
+
+
+def _sonata_rows(x, what):
+    require_cuda(x)
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise PtcoreError(f"{what}: logits must be [N, K] in fp32, fp16 or bf16, got {tuple(x.shape)} {x.dtype}")
+    if not sonata_supported(x.shape[1]):
+        raise PtcoreError(f"{what}: K={x.shape[1]} is not a multiple of 64 in [64, 8192]")
+    return x.detach().contiguous()
+
+
+def _sonata_pairs(match_index, what):
+    require_cuda(match_index)
+    if match_index.dim() != 2 or match_index.shape[1] != 2:
+        raise PtcoreError(f"{what}: match_index must be [M, 2]")
+    return match_index.to(torch.int64).contiguous()
+
+
+def _sonata_vec(v, n, what):
+    require_cuda(v)
+    if v.shape != (n,):
+        raise PtcoreError(f"{what}: expected a vector of {n}, got {tuple(v.shape)}")
+    return v.detach().to(torch.float32).contiguous()
+
+
+def _sonata_partials(m: int, k: int, max_groups: int, device):
+    return torch.empty((int(lib().ptc_sonata_groups(m, k, int(max_groups))), k), dtype=torch.float32, device=device)
+
+
+def sonata_colsum(teacher_sim, match_index, temp: float, b=None, max_groups: int = 0):
+    """r [K] fp32 = sum_i exp(teacher_sim[match_index[i, 1]] / temp) b_i (b = None: 1).  One partial row per workgroup (at most
+    max_groups of them, 0 = the default) summed in index order: bit-reproducible.  Zeros for an empty match_index."""
+    t, mi = _sonata_rows(teacher_sim, "sonata_colsum"), _sonata_pairs(match_index, "sonata_colsum")
+    m, k = mi.shape[0], t.shape[1]
+    r = torch.zeros(k, dtype=torch.float32, device=t.device)
+    if m == 0:
+        return r
+    bb = None if b is None else _sonata_vec(b, m, "sonata_colsum")
+    part = _sonata_partials(m, k, max_groups, t.device)
+    check(lib().ptc_sonata_colsum(ptr(t), dtype_code(t), t.shape[0], ptr(mi), m, k, float(temp), ptr(bb), int(max_groups), ptr(part), ptr(r),
+                                  stream_ptr()), "ptc_sonata_colsum")
+    return r
+
+
+def sonata_rowpass(teacher_sim, match_index, temp: float, a, n: float, want_colsum: bool = True, max_groups: int = 0):
+    """From the prototype scales a [K]: (c [M] = sum_k e_ik a_k, b [M] = 1 / (n c), r [K] = sum_i e_ik b_i or None) in one pass over
+    the gathered teacher rows; n = the global number of rows."""
+    t, mi = _sonata_rows(teacher_sim, "sonata_rowpass"), _sonata_pairs(match_index, "sonata_rowpass")
+    m, k = mi.shape[0], t.shape[1]
+    av = _sonata_vec(a, k, "sonata_rowpass")
+    c = torch.zeros(m, dtype=torch.float32, device=t.device)
+    b = torch.zeros(m, dtype=torch.float32, device=t.device)
+    r = torch.zeros(k, dtype=torch.float32, device=t.device) if want_colsum else None
+    if m == 0:
+        return c, b, r
+    part = _sonata_partials(m, k, max_groups, t.device) if want_colsum else None
+    check(lib().ptc_sonata_rowpass(ptr(t), dtype_code(t), t.shape[0], ptr(mi), m, k, float(temp), ptr(av), float(n), ptr(c), ptr(b),
+                                   int(max_groups), ptr(part), ptr(r), stream_ptr()), "ptc_sonata_rowpass")
+    return c, b, r
+
+
+def sonata_distill_fwd(teacher_sim, student_sim, match_index, student_batch, num_scenes: int, temp: float, student_temp: float, a,
+                       max_groups: int = 0):
+    """The last row pass fused with the loss (sonata_v1m1_base.py:443-454) -> (loss [1] fp32, scene_mean [num_scenes], state for
+    sonata_distill_bwd).  num_scenes bounds student_batch; match_index must be non-empty and listed by ascending scene."""
+    t, s = _sonata_rows(teacher_sim, "sonata_distill_fwd"), _sonata_rows(student_sim, "sonata_distill_fwd")
+    mi = _sonata_pairs(match_index, "sonata_distill_fwd")
+    m, k, dev = mi.shape[0], t.shape[1], t.device
+    if s.shape[1] != k or m < 1:
+        raise PtcoreError(f"sonata_distill_fwd: teacher K={k}, student K={s.shape[1]}, {m} pairs (at least one)")
+    require_cuda(student_batch)
+    sb = student_batch.to(torch.int64).contiguous()
+    if sb.shape != (s.shape[0],):
+        raise PtcoreError("sonata_distill_fwd: student_batch must list one scene per student row")
+    av = _sonata_vec(a, k, "sonata_distill_fwd")
+    vec = torch.zeros((4, m), dtype=torch.float32, device=dev)          # c, lse, row loss, row weight
+    scene_mean = torch.zeros(int(num_scenes), dtype=torch.float32, device=dev)
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    check(lib().ptc_sonata_distill_fwd(ptr(t), dtype_code(t), t.shape[0], ptr(s), dtype_code(s), s.shape[0], ptr(mi), ptr(sb), int(num_scenes), m,
+                                       k, float(temp), float(student_temp), ptr(av), int(max_groups), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
+                                       ptr(vec[3]), ptr(scene_mean), ptr(loss), stream_ptr()), "ptc_sonata_distill_fwd")
+    return loss, scene_mean, (t, s, mi, av, vec)
+
+
+def sonata_distill_bwd(state, temp: float, student_temp: float, dloss, max_groups: int = 0):
+    """d loss / d student_sim [Ns, K] in the student's dtype: matched rows written by the kernel, every other row exactly zero"""
+    t, s, mi, av, vec = state
+    dpred = torch.zeros_like(s)
+    g = dloss.detach().to(torch.float32).reshape(1).contiguous()
+    check(lib().ptc_sonata_distill_bwd(ptr(t), dtype_code(t), t.shape[0], ptr(s), dtype_code(s), s.shape[0], ptr(mi), mi.shape[0], t.shape[1],
+                                       float(temp), float(student_temp), ptr(av), ptr(vec[0]), ptr(vec[1]), ptr(vec[3]), ptr(g),
+                                       int(max_groups), ptr(dpred), stream_ptr()), "ptc_sonata_distill_bwd")
+    return dpred
+
+
+def sonata_patch_rank(grid_coord: torch.Tensor, batch: torch.Tensor, n_batch: int):
+    """generate_mask's point_cluster (sonata_v1m1_base.py:298-304): the rank of every point's (batch, cell) row among the sorted
+    unique rows, = torch.unique(cat([batch, grid_coord]), dim=0, sorted=True, return_inverse=True)[1], by one key sort and the
+    run-numbering kernel of the pooling maps.  grid_coord [N, 3] >= 0.  -> (cluster [N] int64, facts [2] int64 ON THE DEVICE:
+    the number of patches, and non-zero when a cell does not fit the key) -- the caller reads both in its one host read."""
+    require_cuda(grid_coord, batch)
+    n = grid_coord.shape[0]
+    bb = max(1, (int(n_batch) - 1).bit_length())
+    cb = min(20, (62 - bb) // 3)
+    gl = grid_coord.to(torch.int64)
+    key = ((((batch.to(torch.int64) << cb) | gl[:, 0]) << cb | gl[:, 1]) << cb | gl[:, 2]).contiguous()
+    order, _ = sort_keys(key[None].contiguous(), 0, 3 * cb + bb, want_inverse=False)
+    order0 = order[0].contiguous()
+    cluster = torch.empty(n, dtype=torch.int64, device=key.device)
+    ncl = torch.empty(1, dtype=torch.int64, device=key.device)
+    nbytes = lib().ptc_pool_maps_workspace_bytes(n)
+    ws = _ws(nbytes, key.device)
+    check(lib().ptc_pool_maps_count(ptr(key), ptr(order0), n, 0, ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr()), "ptc_pool_maps_count")
+    bad = ((gl.amax() >> cb) != 0) | (gl.amin() < 0) if n else ncl.new_zeros(())
+    return cluster, torch.stack([ncl[0], bad.to(torch.int64)])

@@ -260,3 +260,63 @@ def contrastive_views_batch(seeds, sizes, **kw):
     for v in ("view1", "view2"):
         out[f"{v}_offset"] = np.cumsum([sc[f"{v}_coord"].shape[0] for sc in scenes]).astype(np.int64)
     return out
+
+
+def multi_view_crops(seed: int, global_size: int, local_size: int, num_global: int = 2, num_local: int = 4, grid: float = 0.02,
+                     shift=(-1.3, 0.4, -0.2), jitter: float = 0.004):
+    """The views of one indoor scene as MultiViewGenerator + the Sonata config's pipelines leave them
+    (configs/sonata/pretrain-sonata-v1m1-0-base.py): num_global sphere crops of about global_size points around nearby centres and
+    num_local crops of about local_size points around centres inside the first (principal) global crop, each rotated about z,
+    scaled by 0.9 .. 1.1, jittered and voxelised at `grid` (one point per voxel).  Per group: lists of origin_coord (the scene's
+    coordinate before the augmentation, shifted by `shift`), cell (the view's voxel, >= 0) and feat = colour | normal."""
+    rng = np.random.default_rng(seed)
+    s = indoor_scene(seed, int(global_size * 2.5), grid)
+    origin = (s["coord"] + np.asarray(shift, np.float32)).astype(np.float32)
+    n = origin.shape[0]
+    c0 = origin[rng.integers(n)]
+    near = np.argsort(((origin - c0) ** 2).sum(1), kind="stable")
+
+    def crop(centre, take):
+        take = min(take, n)
+        d2 = ((origin - centre) ** 2).sum(1)
+        keep = np.argpartition(d2, take - 1)[:take] if take < n else np.arange(n)
+        a = rng.uniform(0, 2 * np.pi)
+        rot = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+        p = ((origin[keep] - centre) @ rot.T) * rng.uniform(0.9, 1.1) + rng.normal(0, jitter, (keep.shape[0], 3))
+        gc = np.floor(p / grid).astype(np.int64)
+        gc -= gc.min(0)
+        _, first = np.unique((gc[:, 0] * 8192 + gc[:, 1]) * 8192 + gc[:, 2], return_index=True)
+        first = first[rng.permutation(first.shape[0])]
+        keep, gc = keep[first], gc[first]
+        normal = (s["feat"][keep, 3:] @ rot.T).astype(np.float32)
+        return origin[keep], gc, np.concatenate([s["feat"][keep, :3], normal], 1)
+
+    out = {}
+    for group, num, size, spread in (("global", num_global, global_size, global_size // 4), ("local", num_local, local_size, global_size // 2)):
+        views = [crop(c0 if (group == "global" and v == 0) else origin[near[int(rng.integers(0, max(spread, 1)))]], size) for v in range(num)]
+        out[f"{group}_origin_coord"], out[f"{group}_cell"], out[f"{group}_feat"] = (list(x) for x in zip(*views))
+    return out
+
+
+def multi_view_batch(seeds, global_size: int, local_size: int, grid: float = 0.02, **kw):
+    """collated multi_view_crops scenes under the keys Sonata's forward reads: global_* / local_* coord, origin_coord, feat and
+    offset (one entry per view, the views of a scene adjacent), and grid_size (one entry per scene).  The model derives the voxel of a
+    point from coord, trunc((coord - the minimum over the whole group) / grid_size), and two points of a view in one voxel leave the
+    tie order of the serialization sort to the implementation.  So that a fixture has one answer, coord = (cell + 1.5 + u) grid with
+    |u| <= 0.1, and the first view of each group starts with an anchor point at 0.05 grid on every axis (zero features, an origin
+    100 m away from the scene: it matches nothing): every other point then lies 0.35 .. 0.55 of a cell inside the voxel cell + 1,
+    one point per voxel, and stays there under a coordinate jitter of up to a quarter of a cell on either point."""
+    scenes = [multi_view_crops(s, global_size, local_size, grid=grid, **kw) for s in seeds]
+    rng = np.random.default_rng(int(seeds[0]) * 7919 + 1)
+    out = {}
+    for group in ("global", "local"):
+        origin = [v for sc in scenes for v in sc[f"{group}_origin_coord"]]
+        feat = [v for sc in scenes for v in sc[f"{group}_feat"]]
+        coord = [((c + 1.5 + rng.uniform(-0.1, 0.1, c.shape)) * grid).astype(np.float32) for sc in scenes for c in sc[f"{group}_cell"]]
+        origin[0] = np.concatenate([origin[0][:1] - np.float32(100.0), origin[0]])
+        feat[0] = np.concatenate([np.zeros_like(feat[0][:1]), feat[0]])
+        coord[0] = np.concatenate([np.full((1, 3), 0.05 * grid, np.float32), coord[0]])
+        out[f"{group}_origin_coord"], out[f"{group}_coord"], out[f"{group}_feat"] = np.concatenate(origin), np.concatenate(coord), np.concatenate(feat)
+        out[f"{group}_offset"] = np.cumsum([v.shape[0] for v in coord]).astype(np.int64)
+    out["grid_size"] = np.full(len(seeds), grid, np.float32)
+    return out
