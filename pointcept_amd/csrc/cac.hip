@@ -607,7 +607,10 @@ extern "C" int ptc_cac_supported(int k, int c) { return k >= 2 && k <= CAC_MAX_K
 
 static inline unsigned cac_tile_grid(int64_t n, int s) {
   int64_t t = ptc_cdiv(n > 0 ? n : 1, CAC_ROWS);
-  const int64_t cap = 2048 / s > 1 ? 2048 / s : 1;
+  int64_t cap = 2048 / s > 1 ? 2048 / s : 1;
+#ifndef __HIPCC__
+  if (const char* e = getenv("PTC_EMU_CAC_TILE_WGS")) { const int v = atoi(e); if (v > 0) cap = v; }   // host emulation only: several tiles per workgroup at test sizes
+#endif
   return (unsigned)(t > cap ? cap : t);
 }
 

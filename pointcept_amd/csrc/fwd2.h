@@ -392,6 +392,9 @@ static int launch_fwd2(const void* in, int64_t n_in, const void* w, const float*
     int64_t per_cu = lds > 40 * 1024 ? (F2_PER_CU > 2 ? 2 : F2_PER_CU) : F2_PER_CU;
     if (lds_store) { per_cu = (160 * 1024) / (int64_t)lds; per_cu = per_cu > F2_PER_CU ? F2_PER_CU : (per_cu < 1 ? 1 : per_cu); }
     int64_t gx = 256 * per_cu / (nblk / nh);
+#ifndef __HIPCC__
+    if (const char* e = getenv("PTC_EMU_LINEAR2_WGS")) gx = atoi(e);   // host emulation only: few workgroups = several row tiles each at test sizes
+#endif
     if (gx > tiles) gx = tiles;
     if (gx < 1) gx = 1;
     dim3 grid((unsigned)gx, (unsigned)(nblk / nh));

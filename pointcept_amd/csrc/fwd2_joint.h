@@ -213,6 +213,9 @@ static int launch_linear_joint(const void* in, int64_t n_in, const void* w, cons
 #endif
   per_cu = per_cu > F2_PER_CU ? F2_PER_CU : (per_cu < 1 ? 1 : per_cu);
   int64_t gx = 256 * per_cu;
+#ifndef __HIPCC__
+  if (const char* e = getenv("PTC_EMU_LINEAR2_WGS")) gx = atoi(e);   // host emulation only: few workgroups = several row tiles each at test sizes
+#endif
   if (gx > tiles) gx = tiles;
   if (gx < 1) gx = 1;
   const int S = c_in / 32;

@@ -283,6 +283,10 @@ static int launch_gemm3(const void* in, int64_t n_in, const void* w, const float
   if (n_tiles > 0x7fffffffll) { ptc_set_error("gemm3: %lld tiles", (long long)n_tiles); return PTC_EUNSUPPORTED; }
   int64_t wgs = (n_tiles + 7) & ~(int64_t)7;
   if (wgs > 512) wgs = 512;
+#ifndef __HIPCC__
+  // host emulation only: few workgroups = several tiles each at test sizes (a multiple of 8: one slot per XCD)
+  if (const char* e = getenv("PTC_EMU_GEMM3_WGS")) { const int64_t v = (int64_t)atoi(e) & ~(int64_t)7; if (v >= 8 && v < wgs) wgs = v; }
+#endif
   const dim3 grid((unsigned)wgs);
   const uint32_t in_bytes = (uint32_t)((uint64_t)n_in * c_in * sizeof(T));
 #define G3_LAUNCH_RS(EE, RR)                                                                                                           \

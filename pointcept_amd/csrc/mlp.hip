@@ -327,7 +327,7 @@ mlp_bwd_kernel(const T* __restrict__ dm, const T* __restrict__ x, const T* __res
   load_tile(tile, pd, px);
 #pragma unroll 1
   for (; tile < tiles; tile += gridDim.x) {
-    // (every wave has passed the barriers of the previous tile's chunk loop since it last read DM / Y: the images are free)
+    // (the images are free: the barrier at the end of the previous iteration stands between every wave's last read of DM / Y and these stores)
 #pragma unroll
     for (int i = 0; i < PIECES; ++i) {
       const int q = i * MLPB_THREADS + threadIdx.x, row = q / VPR, pc = q - row * VPR;
@@ -458,6 +458,10 @@ mlp_bwd_kernel(const T* __restrict__ dm, const T* __restrict__ x, const T* __res
         if constexpr (G == 4) dst[1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
       }
     }
+    // With MLPB_HOLD_T = 0 the weight-gradient loop of the LAST chunk re-reads DM / Y (mlp_tr_frag) behind that chunk's final barrier: without
+    // this one a wave that is ahead stores the next tile's rows over images another wave is still contracting over -- wrong dW1 / dW2
+    // whenever a workgroup walks more than one tile (N > 32768 rows).  One barrier per 128-row tile beside the 2 NCH of the chunk loop.
+    __syncthreads();
   }
 
   // ---- this workgroup's partials: every weight-gradient tile is owned by exactly one wave ---------------------------------------------

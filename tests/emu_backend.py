@@ -37,6 +37,9 @@ def build(verbose: bool = False):
     import re
     import shutil
 
+    def substitute(txt):
+        return re.sub(r"\b__shared__\b", "static", re.sub(r"extern\s+__shared__", "extern", txt))
+
     root = os.path.dirname(HERE)
     d = tempfile.mkdtemp(prefix="ptc_emu_")
     csrc = os.path.join(d, "pointcept_amd", "csrc")
@@ -46,16 +49,17 @@ def build(verbose: bool = False):
     for f in glob.glob(os.path.join(root, "pointcept_amd", "csrc", "*.h")) + glob.glob(os.path.join(root, "pointcept_amd", "csrc", "*.inc")) + \
             glob.glob(os.path.join(root, "pointcept_amd", "csrc", "*.hip")) + \
             glob.glob(os.path.join(root, "pointcept_amd", "csrc", "*.cpp")):
-        txt = open(f).read()
-        txt = re.sub(r"extern\s+__shared__", "extern", txt)
-        txt = re.sub(r"\b__shared__\b", "static", txt)
-        open(os.path.join(csrc, os.path.basename(f)), "w").write(txt)
+        open(os.path.join(csrc, os.path.basename(f)), "w").write(substitute(open(f).read()))
     shim = os.path.join(HERE, "host_emulation")
     open(os.path.join(csrc, "emu_runtime.cpp"), "w").write(_RUNTIME_CPP)
     units = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "core.cpp"), os.path.join(csrc, "emu_runtime.cpp")]
     units = [u for u in units if os.path.basename(u) != "host_probe.cpp"]
     if FILES is not None:
         units = [u for u in units if os.path.basename(u) in FILES or u.endswith(".cpp")]
+    # the emulator's own test kernels (tests/host_emulation/*.hip: in this library only, never in the product build)
+    for f in sorted(glob.glob(os.path.join(shim, "*.hip"))):
+        open(os.path.join(csrc, "emu_" + os.path.basename(f)), "w").write(substitute(open(f).read()))
+        units.append(os.path.join(csrc, "emu_" + os.path.basename(f)))
     objs, procs = [], []
     for u in units:
         o = u + ".o"

@@ -12,6 +12,21 @@
 // reported as a deadlock.  What this models: everything that is a function of program order.  What it does not: timing, memory
 // ordering between waves (fences are no-ops: one lane runs at a time), the rounding ORDER inside an MFMA (fp32 sums, k ascending).
 //
+// Schedules (PTC_EMU_SCHED, read at every launch; unset = lockstep).  How the scheduler picks the lanes it resumes in one pass:
+//     lockstep    every runnable lane, lane 0 first: all waves advance together from collective to collective.  Two waves can then never
+//                 be further apart than one collective, so a workgroup barrier that is MISSING between a wave's read and another
+//                 wave's later write of the same LDS bytes does not show.
+//     wave_asc    only the lanes of the LOWEST-numbered wave that has a runnable lane
+//     wave_desc   only the lanes of the HIGHEST-numbered such wave
+// In the two wave-skewed schedules one wave runs on alone -- through its wave collectives, which need nobody else -- until every lane
+// of it is parked at a workgroup barrier or has finished; only then does the next wave move.  That is the largest skew between the
+// waves of a workgroup that its barriers permit, once with the low waves ahead and once with the high ones.  The release rules of the
+// wave collectives, of diverged waves and of the workgroup barrier, and the deadlock reports, are the same in all three.
+// What the skewed schedules model: whether the workgroup barriers in the source are SUFFICIENT to order the waves of one workgroup, for
+// LDS and for global scratch that is private to a workgroup: a result that differs from the lockstep one (or from the oracle) names a
+// missing barrier.  What they still do not model: memory ordering (a store is visible at once), the completion of asynchronous
+// global -> LDS transfers (they land at once), and anything ACROSS workgroups (they run one after the other in every schedule).
+//
 // The sources are compiled unmodified except for one mechanical token substitution done by the build script
 // (tests/emu_backend.py): `extern __shared__` -> `extern`, every other `__shared__` -> `static` (one workgroup at a time, so a
 // function-static array IS the workgroup's LDS).
@@ -84,6 +99,7 @@ struct State {
   void* sched_sp = nullptr;
   dim3 block_idx, block_dim, grid_dim;
   const std::function<void()>* body = nullptr;
+  int sched = 0;           // PTC_EMU_SCHED: 0 lockstep, 1 wave_asc, 2 wave_desc (see the head of the file)
   // PTC_EMU_STATS=1: per launch, the number of lane-level MFMA / transposing-LDS-read / buffer-load executions
   unsigned long long n_mfma = 0, n_tr = 0, n_buf = 0, n_buf_oob = 0, n_shfl = 0;
 };
@@ -134,9 +150,15 @@ inline void run_block() {
   int finished = 0;
   while (finished < n) {
     bool progress = false;
+    int only = -1;           // wave-skewed schedules: the one wave whose lanes this pass resumes
+    for (int i = 0; s.sched != 0 && i < n_waves && only < 0; ++i) {
+      const int w = s.sched == 1 ? i : n_waves - 1 - i;
+      for (int l = 0; l < 64 && w * 64 + l < n; ++l)
+        if (s.lanes[w * 64 + l].state == 0) { only = w; break; }
+    }
     for (int t = 0; t < n; ++t) {
       Lane& L = s.lanes[t];
-      if (L.state != 0) continue;
+      if (L.state != 0 || (only >= 0 && L.wave != only)) continue;
       s.cur = &L;
       emu_switch(&s.sched_sp, L.sp);
       progress = true;
@@ -194,6 +216,13 @@ inline void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void
   s.block_dim = block;
   s.grid_dim = grid;
   s.body = &body;
+  {
+    const char* e = getenv("PTC_EMU_SCHED");
+    if (!e || !*e || !strcmp(e, "lockstep")) s.sched = 0;
+    else if (!strcmp(e, "wave_asc")) s.sched = 1;
+    else if (!strcmp(e, "wave_desc")) s.sched = 2;
+    else { fprintf(stderr, "host emulation: PTC_EMU_SCHED=%s (lockstep | wave_asc | wave_desc)\n", e); abort(); }
+  }
   // canary behind the dynamic LDS the launch asked for: a workgroup that writes past its allocation is reported (on the hardware
   // that is a memory fault or a silent corruption of the neighbouring workgroup's LDS)
   const size_t guard = shmem + 4096 <= (size_t)EMU_LDS ? 4096 : (size_t)EMU_LDS - shmem;

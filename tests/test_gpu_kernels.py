@@ -812,7 +812,7 @@ def test_unpooling_gather_with_addend(cuda, dtype, c):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("c,n", [(64, 3001), (32, 3001), (64, 100), (32, 129)])
-def test_mlp_one_kernel_per_direction(cuda, dtype, c, n, monkeypatch):
+def test_mlp_one_kernel_per_direction(cuda, dtype, c, n, monkeypatch, few_workgroups=None):
     """round 6 (csrc/mlp.hip): the MLP of a PT-v3m1 Block, fc1 -> GELU -> fc2 (+ the residual joint), as ONE kernel per direction with the
     hidden tensor kept on the CU (forward: fc1 accumulators -> GELU -> fc2 operand registers; backward: h recomputed, GELU(h) / dh through LDS
     into the weight gradients).  Against the split kernels it replaces:
@@ -823,8 +823,10 @@ def test_mlp_one_kernel_per_direction(cuda, dtype, c, n, monkeypatch):
     from pointcept_amd import ops
 
     on_gpu = torch.device(cuda).type == "cuda"
-    if not on_gpu:
-        monkeypatch.setenv("PTC_MLP_BWD_WGS", "3")          # emulation: three persistent workgroups = several tiles each at 3001 rows
+    if not on_gpu if few_workgroups is None else few_workgroups:
+        # three / five persistent workgroups = several tiles each at 3001 rows: on the emulation always, on the GPU in
+        # test_mlp_several_tiles_per_workgroup (both launchers read their cap per call)
+        monkeypatch.setenv("PTC_MLP_BWD_WGS", "3")
         monkeypatch.setenv("PTC_MLP_FWD_WGS", "5")
     assert ops.mlp_supported(c, dtype) and not ops.mlp_supported(128, dtype) and not ops.mlp_supported(c, torch.float32)
     g = torch.Generator().manual_seed(c + n)
@@ -873,6 +875,153 @@ def test_mlp_one_kernel_per_direction(cuda, dtype, c, n, monkeypatch):
     for name, got, want in (("dx", dx, xr.grad), ("dw1", dw1, w1r.grad), ("db1", db1, b1r.grad), ("dw2", dw2, w2r.grad), ("db2", db2, b2r.grad)):
         err = float((got.double().cpu() - want).norm() / want.norm())
         assert err < 4 * lo, (name, err)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("c,n,few_workgroups", [(64, 3001, True), (32, 3001, True), (64, 65613, False), (32, 131149, False)])
+def test_mlp_several_tiles_per_workgroup(cuda, dtype, c, n, few_workgroups, monkeypatch):
+    """The body of test_mlp_one_kernel_per_direction where a workgroup of either direction walks SEVERAL tiles on the GPU too: the tile
+    hand-over (the next tile's rows prefetched into registers, the dm / y / GELU(h) / dh images of LDS reused from tile to tile) runs on
+    the hardware, which the emulation's schedules do not model in time.  At n <= 3001 the default grids give every workgroup one tile:
+      3001 rows, 3 backward / 5 forward workgroups   24 backward tiles of 128 rows: 8 each; forward 24 tiles (C = 64: 5 each) or more;
+      65613 rows, C = 64, default grids               forward 513 tiles on 512 workgroups, backward 513 tiles on 256: 2-3 each;
+      131149 rows, C = 32, default grids              forward 1025 tiles on 1024 workgroups, backward 1025 tiles on 256: 4-5 each.
+    (Without the barrier at the end of mlp_bwd_kernel's tile loop a wave that is ahead overwrites the dm / y images another wave is still
+    contracting over: dW1 / dW2 wrong, seen here only if the hardware happens to skew the waves -- the deterministic check of that barrier
+    is tests/test_emulation_wave_skew_cpu.py.)"""
+    test_mlp_one_kernel_per_direction(cuda, dtype, c, n, monkeypatch, few_workgroups=few_workgroups)
+
+
+# ---- the persistent row-wise GEMMs where a workgroup walks THREE tiles or more -----------------------------------------------------------
+# linear2_kernel (fwd2.h), linear2_joint_kernel (fwd2_joint.h) and gemm3_kernel (gemm3.h) hand over from tile to tile inside a workgroup:
+# table entries requested two tiles ahead, rows one tile ahead, LDS stages and register sets reused, gemm3's flat chunk sequence across
+# tile boundaries.  At the row counts of the tests above (n <= 5000 for the first two; fewer tiles than gemm3's 512 workgroups x 3) every
+# workgroup runs ONE tile and none of that executes.  All three are row-wise: a row's result does not depend on the launch it is part of
+# (dispatch is by channel widths), so the big launch must reproduce, BIT FOR BIT, a launch over a short window of its rows alone.
+_BIG_ROWS = 3 * 1024 * 128 + 77          # linear2 / joint: never more than 256 x 4 workgroups of 128-row tiles -- three tiles each and a ragged tail
+
+
+def _windows(n):
+    mid = 128 * (n // 256)               # a tile boundary in the middle of the launch (both 64- and 128-row tiles)
+    return [(0, 333), (mid - 37, mid + 300), (n - 205, n)]
+
+
+def _check_big_rowwise_launch(name, launch, n):
+    """launch(lo, hi) -> outputs [hi - lo, ...] of rows [lo, hi) launched ALONE (one tile per workgroup).  (a) the launch over all rows
+    restricted to each window equals the window's own launch, (c) a second run gives the same bits.  Returns the big launch."""
+    big = launch(0, n)
+    again = launch(0, n)
+    for i, (u, v) in enumerate(zip(big, again)):
+        assert torch.equal(u, v), f"{name}: output {i} not reproducible"
+    for lo, hi in _windows(n):
+        alone = launch(lo, hi)
+        for i, (u, v) in enumerate(zip(big, alone)):
+            assert v.shape[0] == hi - lo
+            bad = (u[lo:hi] != v).reshape(hi - lo, -1).any(1)          # (NaN-free inputs: != is bit inequality up to -0)
+            assert not bool(bad.any()), f"{name}: output {i}, rows {lo}..{hi}: {int(bad.sum())} rows differ from the window launched alone, first {lo + int(torch.nonzero(bad)[0])}"
+    return big
+
+
+def _sample_rows(n, g):
+    return torch.randperm(n, generator=g)[:4096]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin,cout", [(32, 96), (64, 64)])
+def test_linear2_three_tiles_per_workgroup(cuda, dtype, cin, cout):
+    """linear2_kernel, identity rows and through a gather table with absent entries, 393293 rows: (a) row windows, (c) reproducible,
+    (d) 4096 random rows against float64 at the bar of test_linear_identity_table."""
+    from pointcept_amd import ops
+
+    g = torch.Generator().manual_seed(cin + 7 * cout)
+    n = _BIG_ROWS
+    x = torch.randn(n, cin, generator=g).to(dtype)
+    w = (torch.randn(cout, cin, generator=g) / cin ** 0.5).to(dtype)
+    b = torch.randn(cout, generator=g)
+    tab = torch.randint(0, n, (1, n), generator=g).int()
+    tab[0, ::11] = -1                                                  # absent rows: the bias alone
+    xd, wd, bd, td = x.to(cuda), w[:, None, :].contiguous().to(cuda), b.to(cuda), tab.to(cuda)
+    out_i, = _check_big_rowwise_launch("linear2", lambda lo, hi: (ops.spconv_fwd(xd[lo:hi].contiguous(), wd, bd, None),), n)
+    out_t, = _check_big_rowwise_launch("linear2 gathered", lambda lo, hi: (ops.spconv_fwd(xd, wd, bd, td[:, lo:hi].contiguous()),), n)
+    rows = _sample_rows(n, g)
+    rtol, atol = _tols(dtype)
+    _close("linear2_fwd", out_i[rows.to(cuda)], torch.nn.functional.linear(x[rows].double(), w.double(), b.double()), rtol, atol * 4)
+    src = tab[0, rows].long()
+    xg = torch.where((src >= 0)[:, None], x[src.clamp(min=0)].double(), torch.zeros((), dtype=torch.float64))
+    _close("linear2_gathered_fwd", out_t[rows.to(cuda)], torch.nn.functional.linear(xg, w.double(), b.double()), rtol, atol * 4)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("c", [64, 32])
+def test_linear2_joint_three_tiles_per_workgroup(cuda, dtype, c):
+    """linear2_joint_kernel (C -> C with the residual joint and LayerNorm in its epilogue, gather table, DropPath row factors), 393293 rows:
+    (a) row windows, (b) z, y and the LayerNorm statistics bit-identical to ptc_spconv_fwd + ptc_add_norm_fwd, the two launches it replaces
+    (as test_linear_with_the_residual_joint_in_its_epilogue at 3001 rows), (c) reproducible, (d) 4096 random rows against float64."""
+    from pointcept_amd import ops
+
+    g = torch.Generator().manual_seed(c)
+    n = _BIG_ROWS
+    x = torch.randn(n, c, generator=g).to(dtype)
+    w = (torch.randn(c, c, generator=g) / c ** 0.5).to(dtype)
+    b = torch.randn(c, generator=g)
+    a = torch.randn(n, c, generator=g)
+    rs = (torch.rand(n, generator=g) > 0.3).float() / 0.7
+    tab = torch.randint(0, n, (n,), generator=g).int()
+    gam, bet = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g)
+    xd, wd, bd, ad, rd, td = (t.to(cuda) for t in (x, w, b, a, rs, tab))
+    norm = (gam.to(cuda), bet.to(cuda), 1e-5)
+
+    def launch(lo, hi):
+        z, y, st = ops.linear_joint_fwd(xd, wd, bd, td[lo:hi].contiguous(), ad[lo:hi].contiguous(), rd[lo:hi].contiguous(), norm, dtype)
+        return z, y, st.t()
+
+    z, y, st = _check_big_rowwise_launch("linear2_joint", launch, n)
+    u = ops.spconv_fwd(xd, wd[:, None, :].contiguous(), bd, td[None, :].contiguous())
+    z2, y2, _, st2 = ops.add_norm_fwd(u, ad, rd, None, norm, dtype)
+    assert torch.equal(z, z2) and torch.equal(y, y2) and torch.equal(st.t(), st2)
+    # z = a + droppath(u), u = the Linear's output ROUNDED to the feature dtype (the two-launch form's intermediate tensor): the 16-bit bar
+    # on u, scaled by the row factor, plus the fp32 bar on the sum; y against the LayerNorm of the kernel's own z in float64: one rounding
+    rows = _sample_rows(n, g)
+    u_ref = torch.nn.functional.linear(x[tab[rows].long()].double(), w.double(), b.double())
+    ref = a[rows].double() + rs[rows].double()[:, None] * u_ref
+    r16, a16 = _tols(dtype)
+    r32, a32 = _tols(torch.float32)
+    zs = z[rows.to(cuda)].double().cpu()
+    err, tol = (zs - ref).abs(), rs[rows].double()[:, None] * (4 * a16 + r16 * u_ref.abs()) + 4 * a32 + r32 * ref.abs()
+    assert bool((err <= tol).all()), ("joint_z", float((err - tol).max()), float(ref.abs().max()))
+    _close("joint_y", y[rows.to(cuda)], torch.nn.functional.layer_norm(zs, (c,), gam.double(), bet.double(), 1e-5), r16, a16 * 4)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin,cout,kv,n", [(256, 768, 1, 32845), (128, 384, 2, 65741)])
+def test_gemm3_three_tiles_per_workgroup(cuda, dtype, cin, cout, kv, n):
+    """gemm3_kernel: 257 x 6 and 514 x 3 tiles of 128 x 128 on its 512 persistent workgroups -- three tiles or more each, the chunk sequence
+    running across tile boundaries; kv = 2: gathered rows with absent entries (the qkv input gradient's form).  (a) row windows (launched
+    alone they take the 64-row tile form: the tile height never changes a result), (c) reproducible, (d) 4096 random rows against float64."""
+    from pointcept_amd import ops
+
+    g = torch.Generator().manual_seed(cin + kv)
+    n_in = n + 50
+    x = torch.randn(n_in, cin, generator=g).to(dtype)
+    w = (torch.randn(cout, kv, cin, generator=g) / (kv * cin) ** 0.5).to(dtype)
+    b = torch.randn(cout, generator=g)
+    tab = torch.randint(0, n_in, (kv, n), generator=g).int()
+    if kv == 2:
+        tab[1, ::3] = -1
+    xd, wd, bd, td = x.to(cuda), w.to(cuda), b.to(cuda), tab.to(cuda)
+    if kv == 1:
+        launch = lambda lo, hi: (ops.spconv_fwd(xd[lo:hi].contiguous(), wd, bd, None),)       # identity rows (nn.Linear)
+        src = torch.arange(n)[None]
+    else:
+        launch = lambda lo, hi: (ops.spconv_fwd(xd, wd, bd, td[:, lo:hi].contiguous()),)
+        src = tab.long()
+    out, = _check_big_rowwise_launch(f"gemm3 kv={kv}", launch, n)
+    rows = _sample_rows(n, g)
+    idx = src[:, rows]
+    xg = torch.where((idx >= 0)[:, :, None], x[idx.clamp(min=0)].double(), torch.zeros((), dtype=torch.float64))          # [kv, rows, cin]
+    ref = torch.einsum("knc,okc->no", xg, w.double()) + b.double()
+    rtol, atol = _tols(dtype)
+    _close("gemm3_fwd", out[rows.to(cuda)], ref, rtol, atol * 4)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
