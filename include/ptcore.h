@@ -258,8 +258,12 @@ int ptc_spconv_fwd(const void* in, int64_t n_in, const void* weight, const float
  *     hcap a multiple of 16, < 512.
  *   ptc_spconv_fwd_blk: same result as ptc_spconv_fwd(in, ..., nbr, ...) up to the fp32 rounding of a different summation
  *       order, with the input rows of a block staged once in LDS and the weights held in registers.  16-bit dtypes,
- *       kv = 27, c_in = c_out in {32, 64}, bm = 128, hcap = 416, n_in = n_out >= 4096; any other shape is forwarded to
- *       ptc_spconv_fwd.
+ *       kv = 27, bm = 128, n_in = n_out, and either c_in = c_out in {32, 64}, hcap = 416, n_out >= 4096 (csrc/conv7.h) or c_in a
+ *       multiple of 32 in [96, 1024], c_out a multiple of 32 up to 1024, 16 <= hcap <= 511, n_out >= 256 (csrc/conv8.h, round 6;
+ *       PTC_CONV8=0 in the environment turns it off); any other shape is forwarded to ptc_spconv_fwd.  The wide form rewrites the
+ *       weights into MFMA fragment order in `workspace` on every call: workspace >= ptc_spconv_fwd_blk_workspace_bytes
+ *       (c_out * 27 * c_in * 2 bytes rounded up to 256 in the wide channel range, else 0; a function of kv and the channel counts
+ *       alone, n_out is ignored), 16-byte aligned -- PTC_EWORKSPACE when it is NULL or too small; the other forms ignore it.
  *   ptc_spconv_wgrad_blk (round 4): dw of the same convolution (= ptc_spconv_wgrad(in, dout, nbr) without the bias gradient, up to
  *       the fp32 rounding of a different summation order; bit-reproducible) with the whole gradient held in MFMA accumulators
  *       of persistent workgroups and both operands built from the block's LDS images by transposing reads (csrc/wgrad7.h).
@@ -272,7 +276,9 @@ int ptc_rulebook_blocks(const int32_t* nbr, int kv, int64_t n, int bm, int hcap,
                         int32_t* hcnt, int32_t* n_overflow, ptc_stream_t stream);
 int ptc_spconv_fwd_blk(const void* in, int64_t n_in, const void* weight, const float* bias, const int32_t* nbr,
                        const void* tab, const int32_t* hid, const int32_t* hcnt, int bm, int hcap, int64_t n_out,
-                       int kv, int c_in, int c_out, int dtype, void* out, ptc_stream_t stream);
+                       int kv, int c_in, int c_out, int dtype, void* out, void* workspace, size_t workspace_bytes,
+                       ptc_stream_t stream);
+size_t ptc_spconv_fwd_blk_workspace_bytes(int64_t n_out, int kv, int c_in, int c_out);
 size_t ptc_spconv_wgrad_blk_workspace_bytes(int64_t n_out, int kv, int c_in, int c_out);
 int ptc_spconv_wgrad_blk(const void* in, int64_t n_in, const void* dout, const int32_t* nbr, const void* tab, const int32_t* hid,
                          const int32_t* hcnt, const int32_t* n_overflow, int bm, int hcap, int64_t n_out, int kv, int c_in,
@@ -719,8 +725,10 @@ int ptc_pair_aggregate_bwd(const float* grad_out, const float* attn, const float
  *      out [PTC_BLK_O_COUNT]        forward outputs = what the backward reads back (`sv`): caller-allocated
  *      g   [PTC_BLK_GS_COUNT]       backward outputs: gradients (G_*; fp32 parameters' gradients, G_X0 in the dtype of x0, G_XC
  *                                   16-bit) and scratch (S_*), caller-allocated; workspace >= ptc_ptv3_block_workspace_bytes
+ *    The forward takes a workspace too (ABI 3): >= ptc_ptv3_block_fwd_workspace_bytes(n, c), the convolution's
+ *    (ptc_spconv_fwd_blk_workspace_bytes; 0 for 32 / 64 channels, then NULL will do).  Nothing in it outlives the call.
  * ------------------------------------------------------------------------------------------ */
-#define PTC_BLK_ABI 2
+#define PTC_BLK_ABI 3
 enum { PTC_BLK_I_ABI, PTC_BLK_I_N, PTC_BLK_I_NPAD, PTC_BLK_I_NSEQ, PTC_BLK_I_C, PTC_BLK_I_HEADS, PTC_BLK_I_DTYPE, PTC_BLK_I_A_DTYPE,
        PTC_BLK_I_PATCH, PTC_BLK_I_BLK_BM, PTC_BLK_I_BLK_HCAP, PTC_BLK_I_COUNT };
 enum { PTC_BLK_F_SCALE, PTC_BLK_F_EPS_CPE, PTC_BLK_F_EPS_N1, PTC_BLK_F_EPS_N2, PTC_BLK_F_COUNT };
@@ -744,7 +752,9 @@ int ptc_ptv3_block_abi(void);
  * touched and need not be allocated (round 6; PTC_BLK_MLP_FUSED=0 in the environment keeps the split kernels) */
 int ptc_ptv3_block_mlp_fused(int c, int dtype);
 size_t ptc_ptv3_block_workspace_bytes(int64_t n, int64_t n_pad, int c, int heads);
-int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in, void* const* out, ptc_stream_t stream);
+size_t ptc_ptv3_block_fwd_workspace_bytes(int64_t n, int c);
+int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in, void* const* out, void* workspace,
+                       size_t workspace_bytes, ptc_stream_t stream);
 int ptc_ptv3_block_bwd(const int64_t* iv, const float* fv, const void* const* in, const void* const* sv, void* const* g,
                        void* workspace, size_t workspace_bytes, ptc_stream_t stream);
 

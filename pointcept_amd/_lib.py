@@ -49,12 +49,14 @@ _SIGNATURES = {
     "ptc_ptv3_block_abi": (c_int, []),
     "ptc_ptv3_block_mlp_fused": (c_int, [c_int, c_int]),
     "ptc_ptv3_block_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int]),
-    "ptc_ptv3_block_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "ptc_ptv3_block_fwd_workspace_bytes": (c_size, [c_i64, c_int]),
+    "ptc_ptv3_block_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "ptc_ptv3_block_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "ptc_rulebook_blocks_tab_bytes": (c_size, [c_i64]),
     "ptc_rulebook_blocks": (c_int, [c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "ptc_spconv_fwd_blk": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int, c_int,
-                                   c_ptr, c_ptr]),
+                                   c_ptr, c_ptr, c_size, c_ptr]),
+    "ptc_spconv_fwd_blk_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
     "ptc_spconv_wgrad_blk_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
     "ptc_spconv_wgrad_blk": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int, c_int,
                                      c_ptr, c_ptr, c_size, c_ptr]),

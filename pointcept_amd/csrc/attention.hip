@@ -863,13 +863,6 @@ attn_bwd_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict
 // ================================================================================================
 // host side
 // ================================================================================================
-// dynamic LDS above 64 KB has to be opted into once per kernel
-template <typename K>
-static int allow_big_lds(K kernel, size_t bytes) {
-  PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return PTC_OK;
-}
-
 static size_t fwd_lds_bytes(int lp_max) { return (size_t)lp_max * 32 + (size_t)17 * (lp_max + 8) * 2 + AT_WAVES * 4; }
 // (PTC_AT_BWD_PAD_LDS: occupancy probe of tools only -- extra dynamic LDS per workgroup, e.g. 20000 = one workgroup per CU)
 static size_t at_bwd_pad() { const char* e = getenv("PTC_AT_BWD_PAD_LDS"); return e ? (size_t)atoi(e) : 0; }
@@ -908,7 +901,7 @@ extern "C" int ptc_attn_varlen_fwd(const void* qkv, const int32_t* cu_seqlens, i
   const AtPlan plan = at_plan_host(n_units, lp_max);
 #define AT_FWD_CASE(F16)                                                                                                                   \
   if ((dtype == PTC_F16) == F16) {                                                                                                          \
-    rc = allow_big_lds(attn_fwd_kernel<F16>, lds);                                                                                          \
+    rc = ptc_allow_lds(attn_fwd_kernel<F16>, lds);                                                                                          \
     if (rc != PTC_OK) return rc;                                                                                                            \
     hipLaunchKernelGGL(attn_fwd_kernel<F16>, dim3((unsigned)(8 * at_plan_blocks_per_xcd(n_units, plan))), dim3(AT_THREADS), lds, s,           \
                        (const uint16_t*)qkv, cu_seqlens, H, softmax_scale, total, lp_max, n_units, plan.qs, plan.whole, (uint16_t*)out, lse); \
@@ -949,7 +942,7 @@ extern "C" int ptc_attn_varlen_bwd(const void* qkv, const void* out, const void*
       const unsigned g1 = (unsigned)(8 * ((n_units + 7) / 8));
 #define AT_BWD1_CASE(F16)                                                                                                           \
       if ((dtype == PTC_F16) == F16) {                                                                                              \
-        rc = allow_big_lds((attn_bwd1_kernel<F16>), bwd1_lds_bytes(lp_max));                                                        \
+        rc = ptc_allow_lds((attn_bwd1_kernel<F16>), bwd1_lds_bytes(lp_max));                                                        \
         if (rc != PTC_OK) return rc;                                                                                                \
         hipLaunchKernelGGL((attn_bwd1_kernel<F16>), dim3(g1), dim3(AT_THREADS), bwd1_lds_bytes(lp_max), s, (const uint16_t*)qkv,     \
                            (const uint16_t*)out, (const uint16_t*)dout, lse, cu_seqlens, H, softmax_scale, total, lp_max, n_units,  \
@@ -968,9 +961,9 @@ extern "C" int ptc_attn_varlen_bwd(const void* qkv, const void* out, const void*
   //  accumulated in LDS tiles under a turn counter -- was 2.1-2.3 ms against 1.56, r01_w/x: the one-pass kernel above is a different design)
 #define AT_BWD_CASE(LP, F16)                                                                                                        \
   if ((LP == 0 ? lp_max != 1024 : lp_max == LP) && (dtype == PTC_F16) == F16) {                                                                                                             \
-    rc = allow_big_lds((attn_bwd_dq_kernel<LP, F16>), dq_lds_bytes(lp_max));                                                           \
+    rc = ptc_allow_lds((attn_bwd_dq_kernel<LP, F16>), dq_lds_bytes(lp_max));                                                           \
     if (rc != PTC_OK) return rc;                                                                                               \
-    rc = allow_big_lds((attn_bwd_dkv_kernel<LP, F16>), dkv_lds_bytes(lp_max));                                                         \
+    rc = ptc_allow_lds((attn_bwd_dkv_kernel<LP, F16>), dkv_lds_bytes(lp_max));                                                         \
     if (rc != PTC_OK) return rc;                                                                                               \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<LP, F16>), dim3(grid), dim3(AT_THREADS), dq_lds_bytes(lp_max), s, (const uint16_t*)qkv,     \
                        (const uint16_t*)out, (const uint16_t*)dout, lse, cu_seqlens, H, softmax_scale, total, lp_max, n_units, \
@@ -1015,7 +1008,7 @@ extern "C" int ptc_attn_varlen_dropout_fwd(const void* qkv, const int32_t* cu_se
   const unsigned grid = (unsigned)(8 * ((n_units + 7) / 8));
 #define AD_FWD_CASE(F16)                                                                                                             \
   if ((dtype == PTC_F16) == F16) {                                                                                                   \
-    rc = allow_big_lds(attn_drop_fwd_kernel<F16>, lds);                                                                              \
+    rc = ptc_allow_lds(attn_drop_fwd_kernel<F16>, lds);                                                                              \
     if (rc != PTC_OK) return rc;                                                                                                     \
     hipLaunchKernelGGL(attn_drop_fwd_kernel<F16>, dim3(grid), dim3(AT_THREADS), lds, (hipStream_t)stream, (const uint16_t*)qkv,      \
                        cu_seqlens, H, softmax_scale, total, lp_max, n_units, thresh, rp, (uint32_t)seed, (uint32_t)(seed >> 32),     \
@@ -1051,9 +1044,9 @@ extern "C" int ptc_attn_varlen_dropout_bwd(const void* qkv, const void* out, con
   const size_t lds_q = (size_t)lp_max * 64, lds_kv = (size_t)lp_max * 64 + (size_t)lp_max * 8;
 #define AD_BWD_CASE(F16)                                                                                                             \
   if ((dtype == PTC_F16) == F16) {                                                                                                   \
-    rc = allow_big_lds(attn_drop_bwd_dq_kernel<F16>, lds_q);                                                                         \
+    rc = ptc_allow_lds(attn_drop_bwd_dq_kernel<F16>, lds_q);                                                                         \
     if (rc != PTC_OK) return rc;                                                                                                     \
-    rc = allow_big_lds(attn_drop_bwd_dkv_kernel<F16>, lds_kv);                                                                       \
+    rc = ptc_allow_lds(attn_drop_bwd_dkv_kernel<F16>, lds_kv);                                                                       \
     if (rc != PTC_OK) return rc;                                                                                                     \
     hipLaunchKernelGGL(attn_drop_bwd_dq_kernel<F16>, dim3(grid), dim3(AT_THREADS), lds_q, s, (const uint16_t*)qkv, (const uint16_t*)out, \
                        (const uint16_t*)dout, lse, cu_seqlens, H, softmax_scale, total, lp_max, n_units, thresh, rp, (uint32_t)seed, \
@@ -1108,7 +1101,7 @@ extern "C" int ptc_attn_varlen_hd_fwd(const void* qkv, const int32_t* cu_seqlens
   hipStream_t s = (hipStream_t)stream;
 #define AH_FWD_CASE(DK, MB, F16)                                                                                                    \
   if (dk == DK && mb == MB && (dtype == PTC_F16) == F16) {                                                                                                  \
-    rc = allow_big_lds(attn_hd_fwd_kernel<DK, MB, F16>, lds);                                                                       \
+    rc = ptc_allow_lds(attn_hd_fwd_kernel<DK, MB, F16>, lds);                                                                       \
     if (rc != PTC_OK) return rc;                                                                                               \
     hipLaunchKernelGGL((attn_hd_fwd_kernel<DK, MB, F16>), dim3((unsigned)(8 * ((n_units * qs + 7) / 8))), dim3(AT_THREADS), lds, s,  \
                        (const uint16_t*)qkv, cu_seqlens, H, head_dim, softmax_scale, total, lp_max, n_units, qs, (uint16_t*)out, \
@@ -1142,9 +1135,9 @@ extern "C" int ptc_attn_varlen_hd_bwd(const void* qkv, const void* out, const vo
   float* delta = (float*)workspace;
 #define AH_BWD_CASE(DK, F16)                                                                                                        \
   if (dk == DK && (dtype == PTC_F16) == F16) {                                                                                                              \
-    rc = allow_big_lds(attn_hd_bwd_dq_kernel<DK, F16>, hd_dq_lds(DK, lp_max));                                                      \
+    rc = ptc_allow_lds(attn_hd_bwd_dq_kernel<DK, F16>, hd_dq_lds(DK, lp_max));                                                      \
     if (rc != PTC_OK) return rc;                                                                                               \
-    rc = allow_big_lds(attn_hd_bwd_dkv_kernel<DK, F16>, hd_dkv_lds(DK, lp_max));                                                    \
+    rc = ptc_allow_lds(attn_hd_bwd_dkv_kernel<DK, F16>, hd_dkv_lds(DK, lp_max));                                                    \
     if (rc != PTC_OK) return rc;                                                                                               \
     hipLaunchKernelGGL((attn_hd_bwd_dq_kernel<DK, F16>), dim3(grid), dim3(AT_THREADS), hd_dq_lds(DK, lp_max), s,                    \
                        (const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, cu_seqlens, H, head_dim,        \
@@ -1184,7 +1177,7 @@ extern "C" int ptc_attn_varlen_hd_rope_fwd(const void* qkv, const int32_t* cu_se
   const AhRope rp{xyz, inv_freq};
 #define AH_RF_CASE(F16)                                                                                                                \
   if ((dtype == PTC_F16) == F16) {                                                                                                     \
-    rc = allow_big_lds(attn_hd_fwd_kernel<2, 1, F16, true>, lds);                                                                      \
+    rc = ptc_allow_lds(attn_hd_fwd_kernel<2, 1, F16, true>, lds);                                                                      \
     if (rc != PTC_OK) return rc;                                                                                                       \
     hipLaunchKernelGGL((attn_hd_fwd_kernel<2, 1, F16, true>), dim3((unsigned)(8 * ((n_units * qs + 7) / 8))), dim3(AT_THREADS), lds,     \
                        (hipStream_t)stream, (const uint16_t*)qkv, cu_seqlens, H, head_dim, softmax_scale, total, lp_max, n_units, qs,  \
@@ -1219,9 +1212,9 @@ extern "C" int ptc_attn_varlen_hd_rope_bwd(const void* qkv, const void* out, con
   const AhRope rp{xyz, inv_freq};
 #define AH_RB_CASE(F16)                                                                                                                \
   if ((dtype == PTC_F16) == F16) {                                                                                                     \
-    rc = allow_big_lds(attn_hd_bwd_dq_kernel<2, F16, true>, lds_q);                                                                    \
+    rc = ptc_allow_lds(attn_hd_bwd_dq_kernel<2, F16, true>, lds_q);                                                                    \
     if (rc != PTC_OK) return rc;                                                                                                       \
-    rc = allow_big_lds(attn_hd_bwd_dkv_kernel<2, F16, true>, lds_kv);                                                                  \
+    rc = ptc_allow_lds(attn_hd_bwd_dkv_kernel<2, F16, true>, lds_kv);                                                                  \
     if (rc != PTC_OK) return rc;                                                                                                       \
     hipLaunchKernelGGL((attn_hd_bwd_dq_kernel<2, F16, true>), dim3(grid), dim3(AT_THREADS), lds_q, s, (const uint16_t*)qkv,              \
                        (const uint16_t*)out, (const uint16_t*)dout, lse, cu_seqlens, H, head_dim, softmax_scale, total, lp_max,        \
@@ -1266,7 +1259,7 @@ extern "C" int ptc_attn_rpe_fwd(const void* qkv, const int32_t* cu_seqlens, cons
     PTC_REQUIRE(lds32 <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_fwd: max_seqlen=%d with pos_bnd=%d does not fit LDS (fp32)", max_seqlen,
                 pos_bnd);
     const int n_units = (int)(n_seq * H);
-    rc = allow_big_lds(attn_rpe_fwd_f32_kernel, lds32);
+    rc = ptc_allow_lds(attn_rpe_fwd_f32_kernel, lds32);
     if (rc != PTC_OK) return rc;
     hipLaunchKernelGGL(attn_rpe_fwd_f32_kernel, dim3((unsigned)(8 * ((n_units + 7) / 8))), dim3(AT_THREADS), lds32, (hipStream_t)stream,
                        (const float*)qkv, cu_seqlens, grid_coord, rpe_table, R, pos_bnd, H, softmax_scale, total, lp_max, n_units,
@@ -1281,7 +1274,7 @@ extern "C" int ptc_attn_rpe_fwd(const void* qkv, const int32_t* cu_seqlens, cons
   // the flash-branch kernels: configs/s3dis/semseg-pt-v3m1-1-rpe.py runs under the reference's fp16 AMP
 #define AR_FWD(F16)                                                                                                                 \
   {                                                                                                                                 \
-    rc = allow_big_lds(attn_rpe_fwd_kernel<F16>, lds);                                                                              \
+    rc = ptc_allow_lds(attn_rpe_fwd_kernel<F16>, lds);                                                                              \
     if (rc != PTC_OK) return rc;                                                                                                    \
     hipLaunchKernelGGL(attn_rpe_fwd_kernel<F16>, dim3((unsigned)(8 * ((n_units + 7) / 8))), dim3(AT_THREADS), lds, (hipStream_t)stream, \
                        (const uint16_t*)qkv, cu_seqlens, grid_coord, rpe_table, R, pos_bnd, H, softmax_scale, total, lp_max, n_units, \
@@ -1327,9 +1320,9 @@ extern "C" int ptc_attn_rpe_bwd(const void* qkv, const void* out, const void* do
     const int n_units = (int)(n_seq * H);
     const unsigned grid = (unsigned)(8 * ((n_units + 7) / 8));
     float* delta = (float*)workspace;
-    rc = allow_big_lds(attn_rpe_bwd_dq_f32_kernel, lq);
+    rc = ptc_allow_lds(attn_rpe_bwd_dq_f32_kernel, lq);
     if (rc != PTC_OK) return rc;
-    rc = allow_big_lds(attn_rpe_bwd_dkv_f32_kernel, lkv);
+    rc = ptc_allow_lds(attn_rpe_bwd_dkv_f32_kernel, lkv);
     if (rc != PTC_OK) return rc;
     hipLaunchKernelGGL(attn_rpe_bwd_dq_f32_kernel, dim3(grid), dim3(AT_THREADS), lq, s, (const float*)qkv, (const float*)out, (const float*)dout,
                        lse, cu_seqlens, grid_coord, rpe_table, R, pos_bnd, H, softmax_scale, total, lp_max, n_units, (float*)dqkv, delta,
@@ -1351,9 +1344,9 @@ extern "C" int ptc_attn_rpe_bwd(const void* qkv, const void* out, const void* do
   float* delta = (float*)workspace;
 #define AR_BWD(F16)                                                                                                                 \
   {                                                                                                                                 \
-    rc = allow_big_lds(attn_rpe_bwd_dq_kernel<F16>, lds_q);                                                                         \
+    rc = ptc_allow_lds(attn_rpe_bwd_dq_kernel<F16>, lds_q);                                                                         \
     if (rc != PTC_OK) return rc;                                                                                                    \
-    rc = allow_big_lds(attn_rpe_bwd_dkv_kernel<F16>, lds_kv);                                                                       \
+    rc = ptc_allow_lds(attn_rpe_bwd_dkv_kernel<F16>, lds_kv);                                                                       \
     if (rc != PTC_OK) return rc;                                                                                                    \
     hipLaunchKernelGGL(attn_rpe_bwd_dq_kernel<F16>, dim3(grid), dim3(AT_THREADS), lds_q, s, (const uint16_t*)qkv, (const uint16_t*)out, \
                        (const uint16_t*)dout, lse, cu_seqlens, grid_coord, rpe_table, R, pos_bnd, H, softmax_scale, total, lp_max,   \

@@ -47,6 +47,7 @@ static BlkWs blk_ws(int64_t n, int64_t n_pad, int c, int heads) {
   up(ptc_add_norm_bwd_workspace_bytes(n, c));
   up(ptc_attn_varlen_bwd_workspace_bytes(n_pad, heads));
   up(ptc_batch_norm_workspace_bytes(n, c));
+  up(ptc_spconv_fwd_blk_workspace_bytes(n, 27, c, c));             // step 1': the input gradient's fragment-ordered weights (wide Blocks)
   w.common = ptc_align_up(w.common, 256);
   w.wg[0] = ptc_spconv_wgrad_workspace_bytes(n, 1, hid, c);        // fc2 (fused MLP: the partials of fc1 AND fc2, below)
   if (ptc_mlp_supported(c, PTC_BF16) && ptc_mlp_bwd_workspace_bytes(n, c) > w.wg[0]) w.wg[0] = ptc_mlp_bwd_workspace_bytes(n, c);
@@ -64,12 +65,18 @@ static BlkWs blk_ws(int64_t n, int64_t n_pad, int c, int heads) {
 extern "C" size_t ptc_ptv3_block_workspace_bytes(int64_t n, int64_t n_pad, int c, int heads) { return blk_ws(n, n_pad, c, heads).total; }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------
-extern "C" int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in, void* const* out, ptc_stream_t s) {
+// workspace of the forward: the convolution's alone (0 for the 32- / 64-channel Blocks; nothing in it outlives the call)
+extern "C" size_t ptc_ptv3_block_fwd_workspace_bytes(int64_t n, int c) { return ptc_spconv_fwd_blk_workspace_bytes(n, 27, c, c); }
+
+extern "C" int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in, void* const* out, void* workspace,
+                                  size_t workspace_bytes, ptc_stream_t s) {
   PTC_REQUIRE(iv && fv && in && out, PTC_EINVAL, "ptc_ptv3_block_fwd: null argument table");
   PTC_REQUIRE(iv[PTC_BLK_I_ABI] == PTC_BLK_ABI, PTC_EINVAL, "ptc_ptv3_block_fwd: argument tables of another ABI revision");
   const int64_t n = iv[PTC_BLK_I_N], np = iv[PTC_BLK_I_NPAD], n_seq = iv[PTC_BLK_I_NSEQ];
   const int c = (int)iv[PTC_BLK_I_C], H = (int)iv[PTC_BLK_I_HEADS], dt = (int)iv[PTC_BLK_I_DTYPE], hid = 4 * c;
   const int a_dt = (int)iv[PTC_BLK_I_A_DTYPE], patch = (int)iv[PTC_BLK_I_PATCH];
+  const size_t ws_need = ptc_ptv3_block_fwd_workspace_bytes(n, c);
+  PTC_REQUIRE(ws_need == 0 || (workspace && workspace_bytes >= ws_need), PTC_EWORKSPACE, "ptc_ptv3_block_fwd: workspace too small");
   // f16 (round 4): the reference's fp16-autocast recipe -- every GEMM, joint and convolution on f16 operands; the window attention
   // keeps its bf16 arithmetic and does the call site's casts (ptv3m1:209,215) in its load / store paths (attention.hip, F16 I/O)
   PTC_REQUIRE(dt == PTC_BF16 || dt == PTC_F16, PTC_EUNSUPPORTED, "ptc_ptv3_block_fwd: 16-bit GEMM operands only");
@@ -82,7 +89,7 @@ extern "C" int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void
   // 1. positional encoding: 3^3 submanifold convolution (ptv3m1:278-284) ...
   RUN(ptc_spconv_fwd_blk(P(in, PTC_BLK_P_XC), n, P(in, PTC_BLK_P_W_CONV), (const float*)P(in, PTC_BLK_P_B_CONV), nbr, P(in, PTC_BLK_P_BLK_TAB),
                          (const int32_t*)P(in, PTC_BLK_P_BLK_HID), (const int32_t*)P(in, PTC_BLK_P_BLK_HCNT), (int)iv[PTC_BLK_I_BLK_BM],
-                         (int)iv[PTC_BLK_I_BLK_HCAP], n, 27, c, c, dt, out[PTC_BLK_O_CONV], s));
+                         (int)iv[PTC_BLK_I_BLK_HCAP], n, 27, c, c, dt, out[PTC_BLK_O_CONV], workspace, workspace_bytes, s));
   // 2 + 3 in ONE launch where the shape allows (fwd2_joint.h, normA form): the Linear (ptv3m1:285), x1 = x0 + LN_cpe(lin), y1 = norm1(x1);
   // `lin` is still written (LN_cpe's backward reads it) but not read back
   if (PTC_BLK_JOINT_EPILOGUE && ptc_linear_joint_supported(c, c, dt)) {
@@ -201,13 +208,14 @@ extern "C" int ptc_ptv3_block_bwd(const int64_t* iv, const float* fv, const void
   // 2'. the Linear of the positional encoding
   calls[4] = PtcWgradCall{P(sv, PTC_BLK_O_CONV), n, g[PTC_BLK_S_DLIN], nullptr, n, 1, c, c, dt, M<float>(g, PTC_BLK_G_W_LIN), M<float>(g, PTC_BLK_G_B_LIN), wgws(4), W.wg[4]};
   RUN(ptc_spconv_fwd(g[PTC_BLK_S_DLIN], n, P(in, PTC_BLK_P_WT_LIN), nullptr, nullptr, n, 1, c, c, dt, g[PTC_BLK_S_DCONV], s));
-  // 1'. the convolution: weight gradient, bias gradient, input gradient over the same table with mirrored weights
+  // 1'. the convolution: weight gradient, bias gradient, input gradient over the same table with mirrored weights (the last two share the
+  // common scratch in stream order; the deferred weight gradients keep their partials in the wg[] regions, never there)
   RUN(ptc_spconv_wgrad_blk_deferred(P(in, PTC_BLK_P_XC), n, g[PTC_BLK_S_DCONV], nbr, P(in, PTC_BLK_P_BLK_TAB), (const int32_t*)P(in, PTC_BLK_P_BLK_HID),
                                     (const int32_t*)P(in, PTC_BLK_P_BLK_HCNT), (const int32_t*)P(in, PTC_BLK_P_BLK_NOVF), (int)iv[PTC_BLK_I_BLK_BM],
                                     (int)iv[PTC_BLK_I_BLK_HCAP], n, 27, c, c, dt, M<float>(g, PTC_BLK_G_W_CONV), wgws(5), W.wg[5], s, &jobs[5]));
   RUN(ptc_column_sum(g[PTC_BLK_S_DCONV], n, c, dt, M<float>(g, PTC_BLK_G_B_CONV), ws, wb, s));
   RUN(ptc_spconv_fwd_blk(g[PTC_BLK_S_DCONV], n, P(in, PTC_BLK_P_WT_CONV), nullptr, nbr, P(in, PTC_BLK_P_BLK_TAB), (const int32_t*)P(in, PTC_BLK_P_BLK_HID),
-                         (const int32_t*)P(in, PTC_BLK_P_BLK_HCNT), (int)iv[PTC_BLK_I_BLK_BM], (int)iv[PTC_BLK_I_BLK_HCAP], n, 27, c, c, dt, g[PTC_BLK_G_XC], s));
+                         (const int32_t*)P(in, PTC_BLK_P_BLK_HCNT), (int)iv[PTC_BLK_I_BLK_BM], (int)iv[PTC_BLK_I_BLK_HCAP], n, 27, c, c, dt, g[PTC_BLK_G_XC], ws, wb, s));
   // the five Linear weight gradients in one grouped launch (their operands -- saved activations and the scratch gradients above -- are
   // all still in place), then the split-K reductions of all six weight gradients in one launch
   if (mlp_fused) RUN(ptc_spconv_wgrad_group(calls + 2, 3, jobs + 2, s));     // (jobs[0], jobs[1]: the MLP kernel's own partials)

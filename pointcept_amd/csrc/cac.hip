@@ -588,13 +588,6 @@ cac_distill_bwd_kernel(const float* __restrict__ pred, const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ entry points
-template <typename Kern>
-static int cac_allow_lds(Kern kernel, size_t bytes) {
-  if (bytes <= 48 * 1024) return PTC_OK;
-  PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return PTC_OK;
-}
-
 static int cac_check(const char* what, int64_t n, int s, int k, int c) {
   PTC_REQUIRE(n >= 0 && s >= 1, PTC_EINVAL, "%s: n=%lld s=%d", what, (long long)n, s);
   PTC_REQUIRE(s <= 512, PTC_EUNSUPPORTED, "%s: %d segments (at most 512)", what, s);
@@ -649,7 +642,7 @@ extern "C" int ptc_cac_pool_fwd(const float* x, const float* logits, const int64
   const dim3 grid((unsigned)W.P, (unsigned)s);
 #define CAC_POOL_LAUNCH(HARD, MAXT)                                                                                                      \
   do {                                                                                                                                   \
-    if (int rc = cac_allow_lds(cac_pool_fwd_kernel<HARD, MAXT>, lds)) return rc;                                                         \
+    if (int rc = ptc_allow_lds(cac_pool_fwd_kernel<HARD, MAXT>, lds)) return rc;                                                         \
     hipLaunchKernelGGL((cac_pool_fwd_kernel<HARD, MAXT>), grid, dim3(CAC_THREADS), lds, st, x, logits, target, offset, n, k, c, Kp,      \
                        conf_thresh, W.part, W.wpart, W.ppart);                                                                           \
   } while (0)
@@ -682,7 +675,7 @@ extern "C" int ptc_cac_pool_bwd(const float* x, const float* logits, const int64
   }
   const int Kp = cac_kp(k);
   const size_t lds = ((size_t)CAC_ROWS * (cac_ld_m(c) + cac_ld_m(Kp)) + Kp) * 4 + (size_t)Kp * 8;
-  if (int rc = cac_allow_lds(cac_pool_bwd_soft_kernel, lds)) return rc;
+  if (int rc = ptc_allow_lds(cac_pool_bwd_soft_kernel, lds)) return rc;
   hipLaunchKernelGGL(cac_pool_bwd_soft_kernel, dim3(cac_tile_grid(n, s), (unsigned)s), dim3(CAC_THREADS), lds, st, x, logits, offset, n, k, c, Kp,
                      conf_thresh, eps, proto, wsum, dproto, dx, dlogits);
   PTC_CHECK_LAUNCH("cac_pool_bwd_soft_kernel");
@@ -740,10 +733,10 @@ extern "C" int ptc_cac_cos_bwd(const float* x, const float* proto, const int64_t
   const size_t lds = ((size_t)CAC_ROWS * (2 * cac_ld_m(c) + cac_ld_m(Kp)) + 2 * CAC_ROWS) * 4;
   const dim3 grid((unsigned)W.P, (unsigned)s);
   if (ntile <= 32) {
-    if (int rc = cac_allow_lds(cac_cos_bwd_kernel<8>, lds)) return rc;
+    if (int rc = ptc_allow_lds(cac_cos_bwd_kernel<8>, lds)) return rc;
     hipLaunchKernelGGL(cac_cos_bwd_kernel<8>, grid, dim3(CAC_THREADS), lds, st, x, W.phat, offset, n, k, c, Kp, cos_temp, dout, dx, W.part);
   } else {
-    if (int rc = cac_allow_lds(cac_cos_bwd_kernel<32>, lds)) return rc;
+    if (int rc = ptc_allow_lds(cac_cos_bwd_kernel<32>, lds)) return rc;
     hipLaunchKernelGGL(cac_cos_bwd_kernel<32>, grid, dim3(CAC_THREADS), lds, st, x, W.phat, offset, n, k, c, Kp, cos_temp, dout, dx, W.part);
   }
   PTC_CHECK_LAUNCH("cac_cos_bwd_kernel");

@@ -320,31 +320,26 @@ static inline bool conv3_supported(int dtype, int kv, int c_in, int c_out, const
   return !(c_in == 32 && c_out % 64 != 0 && c_out % 96 != 0);
 }
 
-// set around a launch_conv3 call by conv8's launcher (conv8.h): the 128-row blocks with a halo count in [0, c3_skip_max] are skipped
-static thread_local const int32_t* c3_skip_hcnt = nullptr;
-static thread_local int c3_skip_max = 0;
+// conv8's follow-up launch (conv8.h): the 128-row blocks with a halo count hcnt[b] in [0, max] were served there and are skipped
+struct C3Skip { const int32_t* hcnt = nullptr; int max = 0; };
 
 template <typename T, int RT, int KPC, int NTILES, bool GEN, bool IDENT = false, bool DEEP = false>
 static int launch_conv3_i(const void* in, int64_t n_in, const void* w, const float* bias, const int32_t* nbr, int64_t n_out, int kv,
-                          int c_in, int c_out, void* out, hipStream_t s) {
+                          int c_in, int c_out, void* out, hipStream_t s, C3Skip skip) {
   const int n_rowblk = (int)ptc_cdiv(n_out, RT * 64);
   const int nblk = n_rowblk * (c_out / (NTILES * 16));
   const size_t lds = 2 * C3_BUF(NTILES);
   auto kern = conv3_kernel<T, RT, KPC, NTILES, GEN, IDENT, DEEP>;
-  static size_t allowed = 48 * 1024;   // per instantiation
-  if (lds > allowed) {
-    PTC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    allowed = lds;
-  }
+  if (int rc = ptc_allow_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((nblk + 7) / 8))), dim3(256), lds, s, (const T*)in, (const T*)w, bias, nbr, n_out, kv,
-                     c_in, c_out, n_rowblk, (T*)out, (uint32_t)((uint64_t)n_in * c_in * sizeof(T)), c3_skip_hcnt, c3_skip_max);
+                     c_in, c_out, n_rowblk, (T*)out, (uint32_t)((uint64_t)n_in * c_in * sizeof(T)), skip.hcnt, skip.max);
   PTC_CHECK_LAUNCH("conv3_kernel");
   return PTC_OK;
 }
 
 template <typename T>
 static int launch_conv3(const void* in, int64_t n_in, const void* w, const float* bias, const int32_t* nbr, int64_t n_out, int kv,
-                        int c_in, int c_out, void* out, hipStream_t s) {
+                        int c_in, int c_out, void* out, hipStream_t s, C3Skip skip = {}) {
   // 64 output channels per workgroup (96 when c_out is a multiple of 96 but not of 64 -- SpUNet's decoder --
   // else 32); 256-row workgroups when they still give every CU a workgroup, else 128-row ones
   int nt = c_out % 64 == 0 ? 4 : (c_out % 96 == 0 ? 6 : 2);
@@ -359,8 +354,8 @@ static int launch_conv3(const void* in, int64_t n_in, const void* w, const float
 #if C3_DEEP
   // few workgroups (the deep stages of indoor scenes): the 128-row x 64-column form with its gathers two chunks ahead (see DEEP above)
   if (kpc == 1 && nt == 4 && !big && ptc_cdiv(n_out, 128) * (c_out / 64) <= C3_DEEP_MAX_WGS) {
-    if (nbr == nullptr) return launch_conv3_i<T, 2, 1, 4, false, true, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
-    return launch_conv3_i<T, 2, 1, 4, false, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
+    if (nbr == nullptr) return launch_conv3_i<T, 2, 1, 4, false, true, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
+    return launch_conv3_i<T, 2, 1, 4, false, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
   }
 #endif
 #if C3_NT8
@@ -372,32 +367,32 @@ static int launch_conv3(const void* in, int64_t n_in, const void* w, const float
   static const long nt8_min = getenv("PTC_C3_NT8_MIN_WGS") ? atol(getenv("PTC_C3_NT8_MIN_WGS")) : C3_NT8_MIN_WGS;
   const bool nt8 = kpc == 1 && c_out % 128 == 0 && ptc_cdiv(n_out, 256) * (c_out / 128) >= nt8_min;
   if (nt8) {
-    if (nbr == nullptr) return launch_conv3_i<T, 4, 1, 8, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
-    return launch_conv3_i<T, 4, 1, 8, false>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
+    if (nbr == nullptr) return launch_conv3_i<T, 4, 1, 8, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
+    return launch_conv3_i<T, 4, 1, 8, false>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
   }
 #if C3_NT8_SMALL
   // the same wide tile on 128-row workgroups for the mid-sized problems (indoor stages 2 / 3: 12 000 .. 50 000 rows): they are bound by the
   // address path too (8 waves x 54 chunks x 8 gathers x ~57 cycles per CU = 85 us at 12 115 rows x 256 channels, measured 99 us), and
   // the 128-column tile halves the gathers per flop
   if (kpc == 1 && c_out % 128 == 0 && ptc_cdiv(n_out, 128) * (c_out / 128) >= C3_NT8_SMALL_MIN_WGS) {
-    if (nbr == nullptr) return launch_conv3_i<T, 2, 1, 8, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
-    return launch_conv3_i<T, 2, 1, 8, false>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
+    if (nbr == nullptr) return launch_conv3_i<T, 2, 1, 8, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
+    return launch_conv3_i<T, 2, 1, 8, false>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
   }
 #endif
 #endif
   if (nbr == nullptr && gen) {   // dense GEMM whose contraction is not a multiple of the 128-wide chunk: identity table + general chunking
 #define C3_IDG_CASE(N)                                                                                                       \
   if (nt == N)                                                                                                             \
-    return (big && N != 6) ? launch_conv3_i<T, 4, 2, N, true, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s)      \
-                           : launch_conv3_i<T, 2, 2, N, true, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
+    return (big && N != 6) ? launch_conv3_i<T, 4, 2, N, true, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip)      \
+                           : launch_conv3_i<T, 2, 2, N, true, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
     C3_IDG_CASE(4) C3_IDG_CASE(2) C3_IDG_CASE(6)
 #undef C3_IDG_CASE
   }
   if (nbr == nullptr) {   // dense GEMM (kv = 1, c_in % 128 == 0): identity-table instances
 #define C3_ID_CASE(N)                                                                                                        \
   if (nt == N)                                                                                                             \
-    return big ? launch_conv3_i<T, 4, 1, N, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s)               \
-               : launch_conv3_i<T, 2, 1, N, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
+    return big ? launch_conv3_i<T, 4, 1, N, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip)               \
+               : launch_conv3_i<T, 2, 1, N, false, true>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
     C3_ID_CASE(4) C3_ID_CASE(2) C3_ID_CASE(6)
 #undef C3_ID_CASE
     ptc_set_error("conv3 (dense): c_in=%d c_out=%d unsupported", c_in, c_out);
@@ -405,15 +400,15 @@ static int launch_conv3(const void* in, int64_t n_in, const void* w, const float
   }
 #define C3_CASE(K, N, G)                                                                                                   \
   if (kpc == K && nt == N && gen == G)                                                                                     \
-    return big ? launch_conv3_i<T, 4, K, N, G>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s)                           \
-               : launch_conv3_i<T, 2, K, N, G>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
+    return big ? launch_conv3_i<T, 4, K, N, G>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip)                           \
+               : launch_conv3_i<T, 2, K, N, G>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
   C3_CASE(1, 4, false) C3_CASE(2, 4, false) C3_CASE(4, 4, false) C3_CASE(2, 4, true)
   C3_CASE(1, 2, false) C3_CASE(2, 2, false) C3_CASE(2, 2, true) C3_CASE(4, 2, false)
   C3_CASE(16, 2, false) C3_CASE(16, 4, false)
   C3_CASE(1, 6, false) C3_CASE(2, 6, false) C3_CASE(2, 6, true)
 #undef C3_CASE
 #define C3_CASE6(K, G)                                                                                                     \
-  if (kpc == K && nt == 6 && gen == G) return launch_conv3_i<T, 2, K, 6, G>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s);
+  if (kpc == K && nt == 6 && gen == G) return launch_conv3_i<T, 2, K, 6, G>(in, n_in, w, bias, nbr, n_out, kv, c_in, c_out, out, s, skip);
   C3_CASE6(4, false) C3_CASE6(16, false)
 #undef C3_CASE6
   ptc_set_error("conv3: c_in=%d c_out=%d unsupported", c_in, c_out);

@@ -244,11 +244,7 @@ static int launch_conv5_i(const void* in, int64_t n_in, const void* w, const flo
   const int nblk = n_rowblk * (c_out / (NTILES * 16));
   const size_t lds = (size_t)2 * 4 * NTILES * (C3_FRAG + C3_FPAD) + (size_t)4 * RT * 16 * C_IN * 2;
   auto kern = conv5_kernel<T, RT, NS, NTILES>;
-  static size_t allowed = 48 * 1024;   // per instantiation
-  if (lds > allowed) {
-    PTC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    allowed = lds;
-  }
+  if (int rc = ptc_allow_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((nblk + 7) / 8))), dim3(256), lds, s, (const T*)in, (const T*)w, bias, nbr, n_out, kv, c_out,
                      n_rowblk, (T*)out, (uint32_t)((uint64_t)n_in * C_IN * sizeof(T)), (uint32_t)((uint64_t)c_out * kv * C_IN * sizeof(T)),
                      only_where_negative);

@@ -12,7 +12,7 @@
 //     (conv7's layout: the table entries of blocks.hip are byte offsets into it); slot HIMG is an all-zero row: "no neighbour" needs no
 //     branch;
 //   * WEIGHTS NEVER TOUCH LDS (third form): a ~3 us pre-pass (conv8_wfrag_kernel) rewrites W into MFMA FRAGMENT ORDER -- [32-column group]
-//     [tap][32-channel step][tile][lane][8] -- so that a wave fetches the A operands of (tap, step) as 1-KB lane-linear loads straight
+//     [tap][32-channel step][tile][lane][8] -- in the CALLER'S workspace (ptc_spconv_fwd_blk_workspace_bytes: the size of W), so that a wave fetches the A operands of (tap, step) as 1-KB lane-linear loads straight
 //     into registers, one tap ahead of its products.  The waves of a workgroup then share nothing but the halo image: NO workgroup
 //     barrier inside the tap loop, every wave skips exactly the taps ITS rows have no neighbour at, and the workgroup's LDS is table +
 //     image = 48 KB: THREE workgroups per CU, whose table / halo-list / row latencies and stores run under each other's products;
@@ -37,7 +37,6 @@
 // Output-stationary, fixed summation order (chunk-major, taps ascending, 32-channel steps ascending): bit-reproducible.  The order differs
 // from conv3's (tap-major): results agree to fp32 summation order, not bit for bit.
 #pragma once
-#include <mutex>
 
 #ifndef C8_HIMG
 #define C8_HIMG 352          // halo rows the LDS image of the 64- / 32-row forms holds (three workgroups per CU; the 128-row form: C8_HIMG_WIDE, below).
@@ -86,6 +85,12 @@ static inline bool conv8_supported(int dtype, int kv, int c_in, int c_out, int b
   return dtype != PTC_F32 && kv == 27 && c_in % 32 == 0 && c_in >= 96 && c_in <= 1024 && c_out % 32 == 0 && c_out <= 1024 && bm == 128 && hcap >= 16 &&
          hcap <= 511 && n_out >= 256;
 }
+// the caller's workspace holds the fragment-ordered weights (16-bit).  A function of the channel counts alone -- not of dtype, tables or
+// PTC_CONV8 -- so that a caller may cache it per shape: 0 wherever conv8_supported says no for every dtype
+static inline size_t conv8_workspace_bytes(int kv, int c_in, int c_out) {
+  if (!conv8_supported(PTC_BF16, kv, c_in, c_out, 128, 416, 256)) return 0;
+  return ptc_align_up((size_t)c_out * 27 * c_in * 2, 256);
+}
 // columns per workgroup: 128 | 96 (every wave all 128 rows of the block), 64 (two waves per 64-row half), 32 (a wave per 32 rows) -- the
 // narrower forms where the wide one would leave CUs without a workgroup (the deep stages: 12115 rows x 256 channels = 190 wide workgroups)
 static inline int conv8_nt(int c_out, int64_t n_blocks) {
@@ -120,27 +125,6 @@ conv8_wfrag_kernel(const T* __restrict__ w, int c_out, int c_in, T* __restrict__
     const int ch = 32 * cg + 16 * ((i >> 2) & 1) + 4 * (i >> 3) + (i & 3);
     reinterpret_cast<uint4*>(wf)[q] = *reinterpret_cast<const uint4*>(w + ((int64_t)ch * 27 + k) * c_in + 16 * ks + 8 * h);
   }
-}
-
-// per-process scratch for the fragment-ordered weights, one buffer per stream that ever called (grown on demand; hipFree waits for the
-// device, so a kernel still reading the old buffer is never cut off).  The library allocates nothing else itself.
-static void* c8_wf_scratch(size_t bytes, hipStream_t s) {
-  struct Slot { hipStream_t s; void* p; size_t n; bool used; };
-  static Slot slots[8] = {};
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  Slot* sl = nullptr;
-  for (auto& x : slots) if (x.used && x.s == s) { sl = &x; break; }
-  if (!sl) for (auto& x : slots) if (!x.used) { sl = &x; sl->used = true; sl->s = s; sl->p = nullptr; sl->n = 0; break; }
-  if (!sl) { sl = &slots[0]; if (sl->p) (void)hipFree(sl->p); sl->p = nullptr; sl->n = 0; sl->s = s; }
-  if (sl->n < bytes) {
-    if (sl->p) (void)hipFree(sl->p);
-    sl->p = nullptr; sl->n = 0;
-    const size_t want = bytes < ((size_t)4 << 20) ? ((size_t)4 << 20) : ptc_align_up(bytes, (size_t)1 << 20);
-    if (hipMalloc(&sl->p, want) != hipSuccess) { sl->p = nullptr; return nullptr; }
-    sl->n = want;
-  }
-  return sl->p;
 }
 
 typedef __attribute__((ext_vector_type(16))) float c8_f32x16;
@@ -397,8 +381,7 @@ static int launch_conv8_i(const void* in, int64_t n_in, const void* wf, const fl
   const int nblk = n_blocks * (c_out / nt);
   const size_t lds = conv8_lds(RT);
   auto kern = conv8_kernel<T, RT>;
-  static bool attr = false;                   // per instantiation
-  if (!attr) { PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+  if (int rc = ptc_allow_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((nblk + 7) / 8))), dim3(C8_THREADS), lds, s, (const T*)in, (const T*)wf, bias, tab, hid, hcnt, n, c_in, c_out,
                      hcap, n_blocks, nt / 32, (T*)out, c8_ablate());
   PTC_CHECK_LAUNCH("conv8_kernel");
@@ -407,10 +390,8 @@ static int launch_conv8_i(const void* in, int64_t n_in, const void* wf, const fl
 
 template <typename T>
 static int launch_conv8(const void* in, int64_t n_in, const void* w, const float* bias, const int32_t* nbr, const uint16_t* tab, const int32_t* hid,
-                        const int32_t* hcnt, int hcap, int64_t n, int c_in, int c_out, void* out, hipStream_t s) {
-  const size_t wbytes = (size_t)c_out * 27 * c_in * sizeof(T);
-  void* wf = c8_wf_scratch(wbytes, s);
-  PTC_REQUIRE(wf != nullptr, PTC_EWORKSPACE, "ptc_spconv_fwd_blk: no device memory for %zu bytes of fragment-ordered weights", wbytes);
+                        const int32_t* hcnt, int hcap, int64_t n, int c_in, int c_out, void* out, void* wf, hipStream_t s) {
+  const size_t wbytes = (size_t)c_out * 27 * c_in * sizeof(T);      // `wf`: conv8_workspace_bytes of the caller's workspace
   const int64_t pieces = (int64_t)wbytes / 16;
   hipLaunchKernelGGL((conv8_wfrag_kernel<T>), dim3((unsigned)(pieces / 256 < 2048 ? ptc_cdiv(pieces, 256) : 2048)), dim3(256), 0, s, (const T*)w, c_out, c_in, (T*)wf);
   PTC_CHECK_LAUNCH("conv8_wfrag_kernel");
@@ -421,9 +402,5 @@ static int launch_conv8(const void* in, int64_t n_in, const void* w, const float
   else rc = launch_conv8_i<T, 1>(in, n_in, wf, bias, tab, hid, hcnt, hcap, n, c_in, c_out, nt, out, s);
   if (rc != PTC_OK || (c8_ablate() & 16)) return rc;      // (bit 16, timing probe: the first launch alone)
   // the blocks whose halo did not fit: conv3 over exactly those (their counts are on the device)
-  c3_skip_hcnt = hcnt;
-  c3_skip_max = c8_himg(nt >= 96 ? 4 : 1);
-  rc = launch_conv3<T>(in, n_in, w, bias, nbr, n, 27, c_in, c_out, out, s);
-  c3_skip_hcnt = nullptr;
-  return rc;
+  return launch_conv3<T>(in, n_in, w, bias, nbr, n, 27, c_in, c_out, out, s, C3Skip{hcnt, c8_himg(nt >= 96 ? 4 : 1)});
 }

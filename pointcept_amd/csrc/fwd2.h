@@ -363,8 +363,7 @@ static int launch_conv2_w(const void* in, int64_t n_in, const void* w, const flo
   const int kg = conv2_kg(kv * (c_in / cc_len), cc_len, NT, WAVES);
   const size_t lds = (((size_t)kg * NT * (cc_len + 8) * 2 + 15) & ~(size_t)15) + (size_t)WAVES * kg * 32 * 4;
   auto kern = conv2_kernel<T, NTILES, 4, WAVES>;
-  if (lds > 48 * 1024)
-    PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (int rc = ptc_allow_lds(kern, lds)) return rc;
   dim3 grid((unsigned)ptc_cdiv(n_out, WAVES * 32), (unsigned)(c_out / NT));
   hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, s, (const T*)in, (const T*)w, bias, nbr, n_out, kv, c_in, c_out, kg,
                      (T*)out, (uint32_t)((uint64_t)n_in * c_in * sizeof(T)));
@@ -403,8 +402,7 @@ static int launch_fwd2(const void* in, int64_t n_in, const void* w, const float*
 #define L2_LAUNCH_X(SS, EE, LL)                                                                                         \
   {                                                                                                                     \
     auto kern = linear2_kernel<T, NTILES, SS, EE, LL>;                                                                      \
-    if (lds > 48 * 1024)                                                                                                \
-      PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    if (int rc = ptc_allow_lds(kern, lds)) return rc;                                                                   \
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const T*)in, (const T*)w, bias, nbr, n_out, c_in, c_out, nh, (T*)out, \
                        (const T*)aux_in, (T*)aux_out, (uint32_t)((uint64_t)n_in * c_in * sizeof(T)));                   \
   }

@@ -222,8 +222,7 @@ static int launch_linear_joint(const void* in, int64_t n_in, const void* w, cons
 #define LJ_CASE(SS)                                                                                                              \
   case SS: if constexpr ((SS) <= 8) {                                                                                            \
     auto kern = linear2_joint_kernel<T, NTILES, SS>;                                                                              \
-    if (lds > 48 * 1024)                                                                                                         \
-      PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
+    if (int rc = ptc_allow_lds(kern, lds)) return rc;                                                                            \
     hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, s, (const T*)in, (const T*)w, bias, nbr, n_out, c_in,            \
                        (uint32_t)((uint64_t)n_in * c_in * sizeof(T)), J);                                                        \
   } break;

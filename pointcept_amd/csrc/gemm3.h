@@ -293,7 +293,7 @@ static int launch_gemm3(const void* in, int64_t n_in, const void* w, const float
   {                                                                                                                                    \
     auto kern = gemm3_kernel<T, EE, RR>;                                                                                               \
     const int lds = 2 * (RR * 32 + G3_BN) * G3_BK * 2;                                                                                 \
-    PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));                \
+    if (int rc = ptc_allow_lds(kern, lds)) return rc;                                                                                  \
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const T*)in, (const T*)w, bias, nbr, n_out, kv, c_in, c_out, (T*)out,           \
                        (const T*)aux_in, (T*)aux_out, in_bytes, n_col, (int)n_tiles);                                                  \
   }

@@ -533,7 +533,7 @@ extern "C" int ptc_mlp_fwd(const void* x, int64_t n, int c, int dtype, const voi
 #define MLP_FWD(T, CC, WW)                                                                                                      \
   {                                                                                                                             \
     auto kern = mlp_fwd_kernel<T, CC, WW>;                                                                                      \
-    PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    \
+    if (int rc = ptc_allow_lds(kern, lds)) return rc;                                                                           \
     hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(WW * 64), lds, (hipStream_t)stream, (const T*)x, (const T*)w1, b1, (const T*)w2, b2, n, \
                        (uint32_t)((uint64_t)n * c * 2), J);                                                                     \
   }
@@ -588,7 +588,7 @@ int ptc_mlp_bwd_deferred(const void* dm, const void* x, int64_t n, int c, int dt
   {                                                                                                                             \
     auto kern = mlp_bwd_kernel<T, CC>;                                                                                          \
     const size_t lds = MlpBwdLds<CC>::total;                                                                                    \
-    PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    \
+    if (int rc = ptc_allow_lds(kern, lds)) return rc;                                                                           \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(MLPB_THREADS), lds, s, (const T*)dm, (const T*)x, (const T*)w1, b1, (const T*)w2t, n, \
                        (uint32_t)((uint64_t)n * c * 2), (T*)dx, part);                                                          \
   }

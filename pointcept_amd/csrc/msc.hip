@@ -960,13 +960,6 @@ NceLayout nce_layout(int64_t P, int C) {
   return Y;
 }
 
-template <typename K>
-int nce_allow_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return PTC_OK;      // only C > 128 (CH = 16, 66.8 KB) has to opt in
-  PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return PTC_OK;
-}
-
 int nce_check(int64_t P, int C) {
   PTC_REQUIRE(P >= 1, PTC_EINVAL, "ptc_msc_nce: P=%lld (needs at least one matched pair)", (long long)P);
   PTC_REQUIRE(P <= NCE_MAX_P, PTC_EUNSUPPORTED, "ptc_msc_nce: P=%lld above %d pairs", (long long)P, NCE_MAX_P);
@@ -1154,7 +1147,7 @@ extern "C" int ptc_msc_nce_fwd(const float* feat1, int64_t n1, const float* feat
   const float inv_t = 1.0f / nce_t;
 #define NCE_FWD(CH)                                                                                                       \
   do {                                                                                                                    \
-    rc = nce_allow_lds(nce_fwd_kernel<CH>, lds);                                                                          \
+    rc = ptc_allow_lds(nce_fwd_kernel<CH>, lds);                                                                          \
     if (rc != PTC_OK) return rc;                                                                                          \
     hipLaunchKernelGGL(nce_fwd_kernel<CH>, grid, dim3(MSC_THREADS), lds, s, an, bn, p, c, inv_t, tiles_per_split, part, diag); \
   } while (0)
@@ -1195,7 +1188,7 @@ extern "C" int ptc_msc_nce_bwd(const float* an, const float* bn, const float* na
   const float inv_t = 1.0f / nce_t;
 #define NCE_BWD(CH)                                                                                                 \
   do {                                                                                                              \
-    rc = nce_allow_lds(nce_bwd_kernel<CH>, lds);                                                                    \
+    rc = ptc_allow_lds(nce_bwd_kernel<CH>, lds);                                                                    \
     if (rc != PTC_OK) return rc;                                                                                    \
     hipLaunchKernelGGL(nce_bwd_kernel<CH>, grid, dim3(MSC_THREADS), lds, s, an, bn, lse, dloss, p, c, inv_t, ga, gb); \
   } while (0)
@@ -1271,7 +1264,7 @@ extern "C" int ptc_msc_csc_nce_fwd(const float* feat1, int64_t n1, const float* 
   const float inv_t = 1.0f / nce_t;
 #define CSC_FWD(CH)                                                                                                              \
   do {                                                                                                                           \
-    rc = nce_allow_lds(csc_fwd_kernel<CH>, lds);                                                                                 \
+    rc = ptc_allow_lds(csc_fwd_kernel<CH>, lds);                                                                                 \
     if (rc != PTC_OK) return rc;                                                                                                 \
     hipLaunchKernelGGL(csc_fwd_kernel<CH>, grid, dim3(MSC_THREADS), lds, s, an, bn, (const float4*)xs1, (const float4*)xs2, start, p, c, nb, \
                        inv_t, r1, r2, part, diag);                                                                               \
@@ -1317,7 +1310,7 @@ extern "C" int ptc_msc_csc_nce_bwd(const float* an, const float* bn, const float
   const float inv_t = 1.0f / nce_t;
 #define CSC_BWD(CH)                                                                                                               \
   do {                                                                                                                            \
-    rc = nce_allow_lds(csc_bwd_kernel<CH>, lds);                                                                                  \
+    rc = ptc_allow_lds(csc_bwd_kernel<CH>, lds);                                                                                  \
     if (rc != PTC_OK) return rc;                                                                                                  \
     hipLaunchKernelGGL(csc_bwd_kernel<CH>, grid, dim3(MSC_THREADS), lds, s, an, bn, (const float4*)xs1, (const float4*)xs2, start, rmax, rinv, \
                        roww, dloss, p, c, nb, inv_t, r1, r2, ga, gb);                                                                   \

@@ -38,6 +38,16 @@ void ptc_set_error(const char* fmt, ...);
     }                                                                                 \
   } while (0)
 
+// Lets `kernel` be launched with `bytes` of dynamic LDS; nothing to do up to the default limit of 48 KB.  Above it the attribute is set on
+// every launch: it is per DEVICE (a process-wide "already done" flag left the second GPU of a process without it) and the
+// call is a host-side table write.
+template <typename K>
+static inline int ptc_allow_lds(K kernel, size_t bytes) {
+  if (bytes <= 48 * 1024) return PTC_OK;
+  PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return PTC_OK;
+}
+
 static inline int64_t ptc_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t ptc_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

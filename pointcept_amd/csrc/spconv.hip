@@ -255,23 +255,28 @@ extern "C" int ptc_spconv_fwd(const void* in, int64_t n_in, const void* weight, 
   return PTC_OK;
 }
 
+extern "C" size_t ptc_spconv_fwd_blk_workspace_bytes(int64_t n_out, int kv, int c_in, int c_out) {
+  (void)n_out;      // (an upper bound over the row counts: calls below conv8's 256 rows need none)
+  return conv8_workspace_bytes(kv, c_in, c_out);
+}
 extern "C" int ptc_spconv_fwd_blk(const void* in, int64_t n_in, const void* weight, const float* bias, const int32_t* nbr,
                                   const void* tab, const int32_t* hid, const int32_t* hcnt, int bm, int hcap, int64_t n_out, int kv,
-                                  int c_in, int c_out, int dtype, void* out, ptc_stream_t stream) {
+                                  int c_in, int c_out, int dtype, void* out, void* workspace, size_t workspace_bytes, ptc_stream_t stream) {
   const bool buf_ok = (uint64_t)n_in * (uint64_t)c_in * ptc_dtype_size(dtype) <= PTC_BUF_MAX_BYTES;
-  // round 6: the wide shapes (c_in >= 96) on the block-staged kernel with streamed weights (conv8.h) -- OPT-IN (PTC_CONV8=1): correct
-  // (tests/test_gpu_kernels.py::test_spconv_fwd_block_staged_wide) but measured slower than conv3's global gathers at every shape of the two
-  // backbones (128 -> 96 at N = 819200: 820 vs 561 us; 256 -> 256 at N = 12115: 123 vs 100 us; profiles/r06_j_conv8_stages.txt, the ablation
-  // in r06_k_conv8_ablation.txt and DESIGN 4.2 say why)
+  // round 6: the wide shapes (c_in >= 96) on the block-staged kernel with streamed weights (conv8.h), its fragment-ordered weights in the
+  // caller's workspace -- ON BY DEFAULT, forward and input gradient; PTC_CONV8=0 in the environment keeps these shapes on conv3's global
+  // gathers (pointcept_amd/config.py; profiles/r06_t_conv8_himg.txt, conv8.h's head and DESIGN 4.2 have the measurements).  Tested by
+  // tests/test_gpu_kernels.py::test_spconv_fwd_block_staged_wide
   const char* c8e = getenv("PTC_CONV8");
   const bool conv8_on = !(c8e && c8e[0] == '0');
   if (conv8_on && buf_ok && tab && hid && hcnt && nbr && n_in == n_out && conv8_supported(dtype, kv, c_in, c_out, bm, hcap, n_out)) {
     PTC_REQUIRE(weight && out && in, PTC_EINVAL, "ptc_spconv_fwd_blk: null buffer");
-    PTC_REQUIRE(((uintptr_t)in % 16 == 0) && ((uintptr_t)weight % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)tab % 16 == 0), PTC_EINVAL,
-                "ptc_spconv_fwd_blk: buffers must be 16-byte aligned");
+    PTC_REQUIRE(workspace && workspace_bytes >= conv8_workspace_bytes(kv, c_in, c_out), PTC_EWORKSPACE, "ptc_spconv_fwd_blk: workspace too small");
+    PTC_REQUIRE(((uintptr_t)in % 16 == 0) && ((uintptr_t)weight % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)tab % 16 == 0) &&
+                ((uintptr_t)workspace % 16 == 0), PTC_EINVAL, "ptc_spconv_fwd_blk: buffers must be 16-byte aligned");
     if (dtype == PTC_BF16)
-      return launch_conv8<bf16_t>(in, n_in, weight, bias, nbr, (const uint16_t*)tab, hid, hcnt, hcap, n_out, c_in, c_out, out, (hipStream_t)stream);
-    return launch_conv8<f16_t>(in, n_in, weight, bias, nbr, (const uint16_t*)tab, hid, hcnt, hcap, n_out, c_in, c_out, out, (hipStream_t)stream);
+      return launch_conv8<bf16_t>(in, n_in, weight, bias, nbr, (const uint16_t*)tab, hid, hcnt, hcap, n_out, c_in, c_out, out, workspace, (hipStream_t)stream);
+    return launch_conv8<f16_t>(in, n_in, weight, bias, nbr, (const uint16_t*)tab, hid, hcnt, hcap, n_out, c_in, c_out, out, workspace, (hipStream_t)stream);
   }
   if (!buf_ok || !tab || !hid || !hcnt || !nbr || n_in != n_out || !conv7_supported(dtype, kv, c_in, c_out, bm, hcap, n_out))
     return ptc_spconv_fwd(in, n_in, weight, bias, nbr, n_out, kv, c_in, c_out, dtype, out, stream);
@@ -702,8 +707,7 @@ template <typename T, int COT, int CIT, int KG>
 static int launch_wgrad2_inst(const W2Plan& p, const void* in, int64_t n_in, const void* dout, const int32_t* nbr, int64_t n_out, int kv,
                               int c_in, int c_out, float* partial, float* bias_partial, hipStream_t s, const int32_t* gate = nullptr) {
   auto kern = wgrad2_kernel<T, COT, CIT, KG>;
-  if (p.lds > 48 * 1024)
-    PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+  if (int rc = ptc_allow_lds(kern, p.lds)) return rc;
   const int nblocks = p.co_blocks * p.ci_blocks, total = p.gx * p.groups * nblocks;
   hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((total + 7) / 8))), dim3(256), p.lds, s, (const T*)in, (const T*)dout, nbr, n_out, kv,
                      c_in, c_out, ptc_cdiv(n_out, W2_ROWS), p.ci_blocks, partial, bias_partial, p.gx, p.groups, nblocks,
@@ -793,7 +797,7 @@ static int launch_wgrad2_group(const PtcWgradCall* const* cs, int m, PtcWgradJob
   }
   for (int q = m; q <= W2_GROUP_MAX; ++q) g.start[q] = grid;
   auto kern = wgrad2_group_kernel<T, 4, 4, 1>;
-  if (lds > 48 * 1024) PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (int rc = ptc_allow_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, g);
   PTC_CHECK_LAUNCH("wgrad2_group_kernel");
   return PTC_OK;

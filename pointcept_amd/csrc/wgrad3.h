@@ -221,11 +221,11 @@ int ptc_wgrad3_launch(int dtype, const W3Group& g, hipStream_t s) {
   if (grid <= 0) return PTC_OK;
   if (dtype == PTC_BF16) {
     auto kern = wgrad3_kernel<bf16_t>;
-    PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_BYTES));
+    if (int rc = ptc_allow_lds(kern, W3_LDS_BYTES)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), W3_LDS_BYTES, s, g);
   } else {
     auto kern = wgrad3_kernel<f16_t>;
-    PTC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_BYTES));
+    if (int rc = ptc_allow_lds(kern, W3_LDS_BYTES)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), W3_LDS_BYTES, s, g);
   }
   PTC_CHECK_LAUNCH("wgrad3_kernel");

@@ -322,7 +322,7 @@ static int launch_wgrad7_i(const void* in, const void* dout, const uint16_t* tab
   const int seqs = wgrad7_splits(n_out, c_in, c_out);
   const int grid = seqs * wgrad7_slices(c_in, c_out);
   auto kern = wgrad7_kernel<T, C, SL>;
-  PTC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W7Geom<C>::LDS));
+  if (int rc = ptc_allow_lds(kern, W7Geom<C>::LDS)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), W7Geom<C>::LDS, s, (const T*)in, (const T*)dout, tab, hid, hcnt, gate, n_out, n_blocks,
                      partial, c_in, c_out);
   PTC_CHECK_LAUNCH("wgrad7_kernel");

@@ -916,7 +916,7 @@ def _blk_plan(n, npad, c, heads, x0_f32, dt=torch.bfloat16):
              g32=[(E[k], v[0]) for k, v in lg.items()], g32s=[(E[k], v[0]) for k, v in lgs.items()], g16=[(E[k], v[0]) for k, v in ls.items()],
              gparam={k: (lg["G_" + k][0] // 4, int(torch.Size(shapes[k]).numel())) for k in _BLK_PARAMS},
              gx0=(lgs["G_X0"][0] // 4 if x0_f32 else ls["G_X0"][0] // 2), gxc=ls["G_XC"][0] // 2,
-             ws=None)
+             ws=None, ws_fwd=None)
     if len(_blk_plans) > 256:
         _blk_plans.clear()
     _blk_plans[key] = p
@@ -993,7 +993,13 @@ class _BlockFn(Function):
         for idx, off in plan["o32"]:
             pout[idx] = b32 + off
         pout[E["O_X3"]], pout[E["O_XB3"]] = x3.data_ptr(), xb3.data_ptr()
-        _lib.check(ops.lib().ptc_ptv3_block_fwd(iv, fv, pin, pout, ops.stream_ptr()), "ptc_ptv3_block_fwd")
+        if plan["ws_fwd"] is None:
+            plan["ws_fwd"] = int(ops.lib().ptc_ptv3_block_fwd_workspace_bytes(n, c))
+        nbytes = plan["ws_fwd"]
+        # transient (the convolution's fragment-ordered weights at 128 channels and more): NOT saved for the backward
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        _lib.check(ops.lib().ptc_ptv3_block_fwd(iv, fv, pin, pout, None if ws is None else ws.data_ptr(), nbytes, ops.stream_ptr()),
+                   "ptc_ptv3_block_fwd")
         ctx.save_for_backward(x0, xc, rs1, rs2, buf16, buf32, x3, xb3, *keep)
         ctx.meta, ctx.plan = meta, plan
         ctx.present = [p is not None for p in params]

@@ -582,6 +582,9 @@ def rulebook_down(indices: torch.Tensor, coord_bits: int, batch_bits: int):
 # ------------------------------------------------------------------------------------------------
 # sparse conv compute
 # ------------------------------------------------------------------------------------------------
+_fwd_blk_ws: dict = {}      # (kv, c_in, c_out) -> ptc_spconv_fwd_blk_workspace_bytes
+
+
 def spconv_fwd(feat: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                nbr: Optional[torch.Tensor], blk: Optional["BlockTables"] = None) -> torch.Tensor:
     """out[o] = bias + sum_k W[:,k,:] . feat[nbr[k][o]].  weight [C_out, kv, C_in] in feat.dtype,
@@ -609,9 +612,13 @@ def spconv_fwd(feat: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     if blk is not None and nbr is not None:
         if blk.nbr.data_ptr() != nbr.data_ptr() or tuple(blk.nbr.shape) != tuple(nbr.shape):
             raise PtcoreError("blk was built from another gather table")
+        nbytes = _fwd_blk_ws.get((kv, c_in, c_out))       # the wide kernel's fragment-ordered weights; a function of the shape alone
+        if nbytes is None:
+            nbytes = _fwd_blk_ws[(kv, c_in, c_out)] = int(lib().ptc_spconv_fwd_blk_workspace_bytes(n_out, kv, c_in, c_out))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device) if nbytes else None
         check(lib().ptc_spconv_fwd_blk(ptr(feat), feat.shape[0], ptr(weight), ptr(bias), ptr(nbr), ptr(blk.tab), ptr(blk.hid),
                                        ptr(blk.hcnt), blk.bm, blk.hcap, n_out, kv, c_in, c_out, dtype_code(feat), ptr(out),
-                                       stream_ptr()), "ptc_spconv_fwd_blk")
+                                       ptr(ws), nbytes, stream_ptr()), "ptc_spconv_fwd_blk")
         return out
     check(lib().ptc_spconv_fwd(ptr(feat), feat.shape[0], ptr(weight), ptr(bias), ptr(nbr), n_out, kv, c_in, c_out,
                                dtype_code(feat), ptr(out), stream_ptr()), "ptc_spconv_fwd")

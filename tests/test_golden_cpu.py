@@ -359,6 +359,34 @@ def test_argument_validation_returns_error_codes():
     assert L.ptc_rope3d(None, 2, None, 10, 4, 20, 100.0, 1.0, None) == -2
     assert L.ptc_pair_dot_fwd(None, None, None, None, None, None, None, 1, 1 << 50, 8, 16, None, None) == -2 and b"too many" in L.ptc_last_error()
     assert L.ptc_pair_dot_fwd(None, None, None, None, None, None, None, 1, 0, 8, 16, None, None) == 0
+    # the wide block-staged convolution (conv8) keeps its fragment-ordered weights in the caller's workspace: size by shape alone, and the
+    # checks come before any launch (dummy 16-byte-aligned pointers, never dereferenced)
+    need = L.ptc_spconv_fwd_blk_workspace_bytes(9000, 27, 128, 96)
+    assert need >= 96 * 27 * 128 * 2 and need % 256 == 0
+    assert L.ptc_spconv_fwd_blk_workspace_bytes(9000, 27, 64, 64) == 0        # conv7's shapes
+    assert L.ptc_spconv_fwd_blk_workspace_bytes(9000, 1, 128, 128) == 0       # forwarded to ptc_spconv_fwd
+    p = 0x10000
+
+    def fwd_blk(ws, ws_bytes):
+        return L.ptc_spconv_fwd_blk(p, 9000, p, None, p, p, p, p, 128, 416, 9000, 27, 128, 96, 2, p, ws, ws_bytes, None)
+
+    assert fwd_blk(None, need) == -4 and b"workspace" in L.ptc_last_error()
+    assert fwd_blk(p, need - 1) == -4 and b"workspace" in L.ptc_last_error()
+    assert fwd_blk(p + 8, need) == -1 and b"aligned" in L.ptc_last_error()
+    # the Block executor's forward: the same workspace, and tables of the previous ABI revision are refused
+    E = _lib.block_enums()
+    assert E["ABI"] == 3 and L.ptc_ptv3_block_abi() == 3
+    assert L.ptc_ptv3_block_fwd_workspace_bytes(2048, 128) == L.ptc_spconv_fwd_blk_workspace_bytes(2048, 27, 128, 128) > 0
+    assert L.ptc_ptv3_block_fwd_workspace_bytes(2048, 64) == 0
+    iv = (ctypes.c_int64 * E["I_COUNT"])()
+    iv[E["I_ABI"]], iv[E["I_N"]], iv[E["I_NPAD"]], iv[E["I_NSEQ"]], iv[E["I_C"]], iv[E["I_HEADS"]] = E["ABI"], 2048, 2048, 1, 128, 8
+    iv[E["I_DTYPE"]], iv[E["I_A_DTYPE"]], iv[E["I_PATCH"]], iv[E["I_BLK_BM"]], iv[E["I_BLK_HCAP"]] = 2, 0, 1024, 128, 416
+    fv = (ctypes.c_float * E["F_COUNT"])()
+    pin = (ctypes.c_void_p * E["P_COUNT"])()
+    pout = (ctypes.c_void_p * E["O_COUNT"])()
+    assert L.ptc_ptv3_block_fwd(iv, fv, pin, pout, None, 0, None) == -4 and b"workspace" in L.ptc_last_error()
+    iv[E["I_ABI"]] = 2
+    assert L.ptc_ptv3_block_fwd(iv, fv, pin, pout, None, 0, None) == -1 and b"ABI" in L.ptc_last_error()
 
 
 def test_ops_refuse_cpu_tensors():

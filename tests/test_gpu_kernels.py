@@ -516,6 +516,36 @@ def test_spconv_fwd_block_staged_wide(cuda, c, ordered, monkeypatch, n_rows=9000
             _close(f"conv8_nobias_{dtype}", nb, ref - bias, rtol, atol)
 
 
+def test_spconv_fwd_block_staged_wide_two_streams(cuda, monkeypatch):
+    """conv8's fragment-ordered weights live in a workspace that ops.spconv_fwd takes from torch's allocator per call (the library keeps no
+    scratch of its own): two weight shapes whose workspaces differ in size, issued alternately on two side streams with no
+    synchronisation in between, give the bits of the default-stream calls."""
+    from pointcept_amd import ops
+
+    monkeypatch.setenv("PTC_CONV8", "1")
+    nbr_d = _t(oops.subm_rulebook(_curve_sorted_indices(3000), 3), cuda)
+    n = nbr_d.shape[1]
+    bt = ops.BlockTables(nbr_d)
+    cases = []
+    for c_in, c_out in ((128, 96), (256, 256)):
+        assert ops.block_plan(c_in, c_out, 27, torch.bfloat16, n) is not None
+        g = torch.Generator().manual_seed(c_in * 131 + c_out)
+        feat = (torch.randn(n, c_in, generator=g) * 0.5).to(torch.bfloat16).to(cuda)
+        w = (torch.randn(c_out, 27, c_in, generator=g) / (27 * c_in) ** 0.5 * 2).to(torch.bfloat16).to(cuda)
+        bias = torch.randn(c_out, generator=g).to(cuda)
+        cases.append((feat, w, bias, ops.spconv_fwd(feat, w, bias, nbr_d, bt)))
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    got = []
+    for i in range(6):                                   # shapes alternate call by call, streams pair by pair: each stream sees both sizes
+        feat, w, bias, _ = cases[i % 2]
+        with torch.cuda.stream(streams[(i // 2) % 2]):
+            got.append(ops.spconv_fwd(feat, w, bias, nbr_d, bt))
+    torch.cuda.synchronize()
+    for i, out in enumerate(got):
+        assert torch.equal(out, cases[i % 2][3]), f"call {i} (shape {i % 2}, stream {(i // 2) % 2})"
+
+
 @pytest.mark.parametrize("c", [32, 64, 128, (128, 96), 256, (192, 64), 96, (32, 64), (96, 32)])
 @pytest.mark.parametrize("ordered", [True, False])
 def test_spconv_wgrad_block_staged(cuda, c, ordered, n_rows=35000):
