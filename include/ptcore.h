@@ -934,6 +934,29 @@ int ptc_cac_distill_bwd(const float* pred, const float* soft, const int64_t* tar
                         const float* stats, const float* dloss, float* dpred, ptc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Point Prompt Training's language-guided head (csrc/ppt.hip; pointcept/models/point_prompt_training/
+ * point_prompt_training_v1m1_language_guided.py:98-107, point_prompt_training_v1m3_neo.py:117-129):
+ *   h = x w^T + b [n,d];  inv = 1 / max(|h|, eps);  logits [n,k] = scale * (h e^T) * inv.   h is never written.
+ * c a multiple of 32 in [32, 128], d a multiple of 64 in [64, 1024], 1 <= k <= 256 (ptc_ppt_head_supported; PTC_EUNSUPPORTED otherwise).
+ * x [n,c] and w [d,c] of `dtype` (16-bit: 16-bit MFMA operands, fp32 accumulation; fp32: the exact-f32 MFMA); b [d], e [k,d] (the
+ * selected class rows), logits, inv_norm [n] fp32.  h e^T runs on the exact-f32 MFMA with h in fp32 for every dtype.
+ * ptc_ppt_head_bwd needs nothing d-wide: with a_i = scale inv_i dlogits_i, rho_i = (dlogits_i . logits_i) inv_i^2 (0 where
+ * |h_i| < eps) and the caller's G = e w [k,c] (fp32), M = w^T w [c,c], u = w^T b [c] (both DOUBLE, formed in double: M x_i + u cancels
+ * where h_i is small against |w| |x_i|, and is accumulated in double) it writes
+ *   dx [n,c] (dtype) = a_i G - rho_i (M x_i + u),   A [k,c] = sum_i a_i x_i^T,   Bm [c,c] = sum_i rho_i x_i x_i^T,   v [c] = sum_i rho_i x_i,
+ *   asum [k] = sum_i a_i,   rsum [1] = sum_i rho_i        (dw = e^T A - w Bm - b v^T,  db = e^T asum - w v - b rsum: the caller's)
+ * reduced over fixed row ranges in a fixed order, no float atomics: bit-reproducible.  The workspace (ptc_ppt_head_workspace_bytes) holds
+ * the backward's partials only: the forward takes none.
+ * ------------------------------------------------------------------------------------------ */
+int ptc_ppt_head_supported(int c, int d, int k, int dtype);
+size_t ptc_ppt_head_workspace_bytes(int64_t n, int c, int d, int k);
+int ptc_ppt_head_fwd(const void* x, const void* w, const float* b, const float* e, int64_t n, int c, int d, int k, int dtype, float scale,
+                     float eps, float* logits, float* inv_norm, ptc_stream_t stream);
+int ptc_ppt_head_bwd(const void* x, const float* dlogits, const float* logits, const float* inv_norm, const float* G, const double* M,
+                     const double* u, int64_t n, int c, int d, int k, int dtype, float scale, float eps, void* dx, float* A, float* Bm, float* v,
+                     float* asum, float* rsum, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SGIFormer-v1m1 query decoder (csrc/sgiformer.hip; pointcept/models/sgiformer/sgiformer_v1m1_base.py, loss.py).
  * A ragged batch of s scenes: cu_q, cu_k, cu_g are int32 [s + 1] row starts of the queries, the keys (superpoints) and the
  * instances.  "Packed" masks hold one bit per (row, column) in uint32 words, ceil(columns / 32) words per row, bit c % 32 of word

@@ -206,6 +206,11 @@ _SIGNATURES = {
     "ptc_lovasz_softmax_rows_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
     "ptc_lovasz_softmax_rows": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
                                         c_ptr, c_size, c_ptr]),
+    "ptc_ppt_head_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "ptc_ppt_head_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
+    "ptc_ppt_head_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr]),
+    "ptc_ppt_head_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_f32, c_f32, c_ptr,
+                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "ptc_sonata_supported": (c_int, [c_int]),
     "ptc_sonata_groups": (c_i64, [c_i64, c_int, c_int]),
     "ptc_sonata_colsum": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_i64, c_int, ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),

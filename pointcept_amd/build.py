@@ -57,6 +57,7 @@ HIP_SOURCES = [
     "cac.hip",
     "sgiformer.hip",
     "sonata.hip",
+    "ppt.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

@@ -83,6 +83,10 @@ OPT_IN_MODEL_CLASSES = {
     "CAC-v1m1": ("context_aware_classifier", "CACSegmentor"),         # context_aware_classifier_v1m1_base.py:17
     "SGIFormer-v1m1": ("sgiformer", "SGIFormer"),                      # sgiformer/sgiformer_v1m1_base.py:482
     "Sonata-v1m1": ("sonata", "Sonata"),                              # sonata/sonata_v1m1_base.py:71
+    "SpUNet-v1m3": ("sparse_unet_v1m3", "SpUNetV1m3"),                # sparse_unet/spconv_unet_v1m3_pdnorm.py:230
+    "PPT-v1m1": ("point_prompt_training", "PointPromptTraining"),     # point_prompt_training_v1m1_language_guided.py:18
+    "PPT-v1m2": ("point_prompt_training", "PointPromptTrainingDecoupled"),   # point_prompt_training_v1m2_decoupled.py:18
+    "PPT-v1m3": ("point_prompt_training", "PointPromptTrainingNeo"),  # point_prompt_training_v1m3_neo.py:23
 }
 
 
@@ -109,7 +113,8 @@ def register_models(registry, names=None, force: bool = True) -> list:
     """Registers the engine's module-level ports in the reference's `MODELS` registry (pointcept/models/builder.py) under the
     names the reference's configs use, replacing the CUDA-library implementations (`force=True`), so that
     `MODELS.build(cfg.model.backbone)` constructs them.  Returns the names registered.  Without `names`: every name of
-    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs, PointGroup, MSC-v1m1 / -v1m2, CAC, SGIFormer, Sonata) only when named.
+    MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs, PointGroup, MSC-v1m1 / -v1m2, CAC, SGIFormer, Sonata, SpUNet-v1m3,
+    PPT-v1m1 / -v1m2 / -v1m3) only when named.
 
         from pointcept.models.builder import MODELS
         import pointcept_amd.compat; pointcept_amd.compat.register_models(MODELS)

@@ -48,6 +48,9 @@ settings), and so a regression can be bisected without a rebuild.
                      gathered teacher rows, exp and three Sinkhorn-Knopp iterations over a dense M x K fp32 matrix, log_softmax of the
                      gathered student rows and their product -- instead of the scaling-vector passes of csrc/sonata.hip (A/B baseline,
                      and the CPU path of the port); view matching and the masks run as knn_query + radius filter and torch.unique
+  PTC_PPT=0          Point Prompt Training's language-guided head (point_prompt_training.py, functional.ppt_head) runs as the
+                     reference's own expression -- proj_head, the row norm, the division and the class matmul, four passes over an
+                     [N, 512] tensor that autograd keeps -- instead of csrc/ppt.hip (A/B baseline, and the CPU path of the port)
   PTC_FUSE_BLOCK=0   the three residual joints of a PTv3 Block run as separate LayerNorm / add / cast
                      kernels instead of the fused add_norm passes
 """
@@ -78,6 +81,7 @@ MSC_KERNELS = _flag("PTC_MSC", True)
 CAC_KERNELS = _flag("PTC_CAC", True)
 SGI_KERNELS = _flag("PTC_SGI", True)
 SONATA_KERNELS = _flag("PTC_SONATA", True)
+PPT_KERNELS = _flag("PTC_PPT", True)
 WGRAD_BLK = _flag("PTC_WGRAD_BLK", True)
 FUSE_BN_TAIL = _flag("PTC_FUSE_BN_TAIL", True)
 BATCH_BN_COUNTERS = _flag("PTC_BATCH_BN_COUNTERS", True)

@@ -30,37 +30,8 @@ from . import functional as PF
 from . import nn as PNN
 from . import ops
 from .compat import build_backbone
+from .criteria import Criteria
 from .structure import Point
-
-
-class _Criteria:
-    """build_criteria(criteria) (losses/builder.py:22-31) on the engine's loss kernels"""
-
-    SUPPORTED = {
-        "CrossEntropyLoss": ("cross_entropy", dict(weight=None, size_average=None, reduce=None, reduction="mean", label_smoothing=0.0)),
-        "LovaszLoss": ("lovasz_softmax", dict(mode="multiclass", class_seen=None, per_image=False)),
-    }
-
-    def __init__(self, cfg):
-        self.terms = []
-        for c in cfg or []:
-            c = dict(c)
-            kind = c.pop("type")
-            w = float(c.pop("loss_weight", 1.0))
-            ignore = int(c.pop("ignore_index", -1))
-            if kind not in self.SUPPORTED:
-                raise ValueError(f"CAC-v1m1 criteria: {kind} is not on the engine's loss kernels")
-            fn, defaults = self.SUPPORTED[kind]
-            other = {k: v for k, v in c.items() if k not in defaults or defaults[k] != v}
-            if other:       # any other setting would silently train a different loss
-                raise ValueError(f"CAC-v1m1 criteria: {kind} with {other} is not on the engine's loss kernels")
-            self.terms.append((getattr(PF, fn), w, ignore))
-
-    def __call__(self, pred, target):
-        loss = 0
-        for fn, w, ignore in self.terms:
-            loss = loss + fn(pred, target, ignore) * w
-        return loss
 
 
 class CACSegmentor(nn.Module):
@@ -83,7 +54,7 @@ class CACSegmentor(nn.Module):
         self.proj = nn.Sequential(PNN.Linear(c * 2, c * 2, bias=False), PNN.ReLU(), PNN.Linear(c * 2, c))
         self.apd_proj = nn.Sequential(PNN.Linear(c * 2, c * 2, bias=False), PNN.ReLU(), PNN.Linear(c * 2, c))
         self.feat_proj_layer = nn.Sequential(PNN.Linear(c, c, bias=False), PNN.BatchNorm1d(c), PNN.ReLU(), PNN.Linear(c, c))
-        self.criteria = criteria if callable(criteria) else _Criteria(criteria)
+        self.criteria = criteria if callable(criteria) else Criteria(criteria, "CAC-v1m1")
         self.last = {}               # integers of the last forward (rows past the gate per scene, class counts), for tests and tools
 
     def _kernels(self, feat: torch.Tensor) -> bool:

@@ -10,6 +10,7 @@ uses floating-point atomics and every result is bit-reproducible run to run:
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 from typing import Optional
@@ -1679,6 +1680,97 @@ def cac_distill_torch(pred, soft, target, smoothness: float = 0.5, eps: float = 
     if len(weight_list) > 0:
         return sum(loss_list) / (sum(weight_list) + 1e-4)
     return torch.zeros(1, dtype=pred.dtype, device=pred.device).mean()
+
+
+# ------------------------------------------------------------------------------------------------
+# Point Prompt Training's language-guided head (point_prompt_training_v1m1_language_guided.py:98-107, _v1m3_neo.py:117-129)
+# ------------------------------------------------------------------------------------------------
+def _ppt_scale(logit_scale) -> float:
+    """exp(logit_scale) as a host float (a tensor costs one device read; point_prompt_training.py caches it per parameter version)"""
+    if isinstance(logit_scale, torch.Tensor):
+        return float(logit_scale.detach().float().exp())
+    return math.exp(float(logit_scale))
+
+
+class _PPTHead(Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, e, logit_scale, scale, eps):
+        dt = _autocast_dtype(x)
+        with torch.autocast(device_type=x.device.type, enabled=False):
+            xc = x.to(dt).contiguous()
+            wc = _cast_cache.get(weight, dt).contiguous()
+            b32 = (bias.float() if bias is not None else torch.zeros(weight.shape[0], dtype=torch.float32, device=x.device)).contiguous()
+            e32 = e.float().contiguous()
+            logits, inv = ops.ppt_head_fwd(xc, wc, b32, e32, scale, eps)
+        ctx.save_for_backward(xc, weight, bias, e32, logits, inv, logit_scale if isinstance(logit_scale, torch.Tensor) else None)
+        ctx.args = (float(scale), float(eps), x.dtype)
+        ctx.mark_non_differentiable(inv)
+        return logits, inv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dlogits, _dinv):
+        xc, weight, bias, e32, logits, inv, logit_scale = ctx.saved_tensors
+        scale, eps, in_dtype = ctx.args
+        need = ctx.needs_input_grad
+        dx = dw = db = ds = None
+        with torch.autocast(device_type=xc.device.type, enabled=False):
+            dl = dlogits.float().contiguous()
+            if need[4] and logit_scale is not None:          # d / d logit_scale of exp(logit_scale) * sim
+                ds = (dl * logits).sum().to(logit_scale.dtype).reshape(logit_scale.shape)
+            if need[0] or need[1] or need[2]:
+                # the small fp32 products around the kernel: [<= 1024, <= 128] matrices
+                w32 = weight.detach().float()
+                b32 = bias.detach().float() if bias is not None else torch.zeros(w32.shape[0], dtype=torch.float32, device=w32.device)
+                w64 = w32.double()          # M x + u cancels where h is small against |W| |x|: formed (and used by the kernel) in double
+                G, M, u = e32 @ w32, w64.t() @ w64, w64.t() @ b32.double()
+                dxc, A, Bm, v, asum, rsum = ops.ppt_head_bwd(xc, dl, logits, inv, G, M, u, w32.shape[0], scale, eps)
+                if need[0]:
+                    dx = dxc.to(in_dtype)
+                if need[1]:
+                    dw = (e32.t() @ A - w32 @ Bm - torch.outer(b32, v)).to(weight.dtype)
+                if need[2] and bias is not None:
+                    db = (e32.t() @ asum - w32 @ v - b32 * rsum).to(bias.dtype)
+        return dx, dw, db, None, ds, None, None          # the class rows arrive detached (a trainable embedding takes ppt_head_torch)
+
+
+def ppt_head_kernels(x: torch.Tensor, weight: torch.Tensor, class_embedding: torch.Tensor, use_kernels=None) -> bool:
+    """whether functional.ppt_head runs csrc/ppt.hip for these operands (else: functional.ppt_head_torch)"""
+    want = bool(config.PPT_KERNELS and x.is_cuda) if use_kernels is None else bool(use_kernels)
+    if not want or x.dim() != 2 or x.shape[0] == 0 or class_embedding.requires_grad:
+        return False
+    dt = _autocast_dtype(x)
+    return dt in (torch.float32, torch.bfloat16, torch.float16) and ops.ppt_head_supported(x.shape[1], weight.shape[0], class_embedding.shape[0], dt)
+
+
+def ppt_head(x, weight, bias, class_embedding, logit_scale, eps: float = 0.0, return_inv_norm: bool = False, use_kernels=None):
+    """seg_logits [N, K] = exp(logit_scale) * normalize(x @ weight.T + bias) @ class_embedding.T of PPT-v1m1 (:98-107, eps = 0: a
+    plain division by the norm) and PPT-v1m3 (:117-129, F.normalize's eps), with class_embedding [K, D] the rows already selected.
+    One kernel per direction (csrc/ppt.hip): the [N, D] projection lives in registers, nothing D-wide is stored or revisited by the
+    backward.  Differentiable in x, weight, bias and, through the outputs, logit_scale (frozen in the reference).
+    The logits are fp32, ALSO under autocast, where the reference returns 16-bit logits (its matmul runs in the autocast dtype on
+    a 16-bit h and a 16-bit normalised h); here 16-bit x and weight feed the MFMA, h and everything after it stay fp32.
+    PTC_PPT=0 (config.PPT_KERNELS), CPU tensors and shapes the kernel refuses (C not a multiple of 32 up to 128, D not a multiple of
+    64 up to 1024, K above 256) take ppt_head_torch, as does a class embedding that requires grad; `use_kernels` overrides the first two.  return_inv_norm: also 1 / max(|h|, eps) [N]."""
+    if not ppt_head_kernels(x, weight, class_embedding, use_kernels):
+        return ppt_head_torch(x, weight, bias, class_embedding, logit_scale, eps, return_inv_norm)
+    logits, inv = _PPTHead.apply(x, weight, bias, class_embedding.detach(), logit_scale, _ppt_scale(logit_scale), float(eps))
+    return (logits, inv) if return_inv_norm else logits
+
+
+def ppt_head_torch(x, weight, bias, class_embedding, logit_scale, eps: float = 0.0, return_inv_norm: bool = False):
+    """the reference's expression, in the dtype (and autocast state) it is called in"""
+    feat = F.linear(x, weight, bias)
+    if eps == 0:
+        feat_n = feat / feat.norm(dim=-1, keepdim=True)                       # v1m1 :99
+    else:
+        feat_n = F.normalize(feat, dim=-1, p=2, eps=eps)                      # v1m3 :120
+    sim = feat_n @ class_embedding.t()
+    scale = logit_scale.exp() if isinstance(logit_scale, torch.Tensor) else math.exp(float(logit_scale))
+    seg_logits = scale * sim
+    if return_inv_norm:
+        return seg_logits, 1.0 / feat.detach().norm(dim=-1).clamp_min(eps)
+    return seg_logits
 
 
 # ------------------------------------------------------------------------------------------------

@@ -119,14 +119,23 @@ class BatchNorm1d(nn.BatchNorm1d):
     `nn.SyncBatchNorm.convert_sync_batchnorm` of the reference trainer's `sync_bn=True` path (pointcept/engines/train.py:257-258),
     quantisers, PEFT wrappers -- simply gets the reference's unfused BatchNorm -> activation sequence."""
 
-    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, act: str = "none") -> torch.Tensor:
-        """residual / act (SpUNet's BasicBlock): act(BN(x) + residual) in the same pass, spconv_unet_v1m1_base.py:79-83"""
-        _require_gpu(x, "BatchNorm1d")
-        use = (self.affine and x.is_cuda and x.dim() == 2 and x.shape[0] > 1 and ops.batch_norm_supported(x.shape[1], x.dtype)
+    def kernel_path(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, need_affine: bool = True) -> bool:
+        """whether forward runs functional.batch_norm_act for this input (else: torch's BatchNorm, then the residual and the activation)"""
+        use = ((self.affine or not need_affine) and x.is_cuda and x.dim() == 2 and x.shape[0] > 1 and ops.batch_norm_supported(x.shape[1], x.dtype)
                and (self.training or self.running_mean is not None))
         if residual is not None and (residual.dtype != x.dtype or residual.shape != x.shape):
             use = False
-        if not use:
+        return bool(use)
+
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, act: str = "none", weight: Optional[torch.Tensor] = None,
+                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """residual / act (SpUNet's BasicBlock): act(BN(x) + residual) in the same pass, spconv_unet_v1m1_base.py:79-83.
+        weight / bias ([C], differentiable): an affine map used INSTEAD of the module's own -- the statistics, their running buffers
+        and the step counter stay the module's (the prompt-driven norm of sparse_unet_v1m3.py folds its modulation in here)"""
+        _require_gpu(x, "BatchNorm1d")
+        if not self.kernel_path(x, residual, need_affine=weight is None):
+            if weight is not None:          # callers ask kernel_path(x, residual, need_affine=False) first and keep their own unfused form
+                raise PtcoreError("pointcept_amd.nn.BatchNorm1d: a weight / bias override needs the kernel path (kernel_path(...) is False)")
             y = super().forward(x)
             if residual is not None:
                 y = y + residual
@@ -143,7 +152,8 @@ class BatchNorm1d(nn.BatchNorm1d):
                 momentum = 1.0 / float(self.num_batches_tracked)
         rm = self.running_mean if (not self.training or self.track_running_stats) else None
         rv = self.running_var if (not self.training or self.track_running_stats) else None
-        return PF.batch_norm_act(x, self.weight, self.bias, rm, rv, training, momentum, self.eps, act, residual)
+        return PF.batch_norm_act(x, self.weight if weight is None else weight, self.bias if bias is None else bias, rm, rv, training, momentum,
+                                 self.eps, act, residual)
 
 
 class GELU(nn.GELU):
@@ -163,6 +173,12 @@ def _global_hooks() -> bool:
     a fused pair would show them one call where the reference shows two"""
     M = torch.nn.modules.module
     return bool(M._global_forward_hooks or M._global_forward_pre_hooks or M._global_backward_hooks or M._global_backward_pre_hooks)
+
+
+def foldable(norm: nn.Module) -> bool:
+    """whether `norm` may take another affine map or a following activation into its own pass: the engine's exact type, no hook on it,
+    no module-global hooks (the conditions fused_act puts on the norm)"""
+    return type(norm) is BatchNorm1d and not _hooked(norm) and not _global_hooks()
 
 
 def fused_act(norm: nn.Module, act: Optional[nn.Module]) -> Optional[str]:

@@ -2047,6 +2047,61 @@ def cac_distill_bwd(state, smoothness: float, eps: float, stats, dloss):
 
 
 # ------------------------------------------------------------------------------------------------
+# Point Prompt Training's language-guided head (csrc/ppt.hip)
+# ------------------------------------------------------------------------------------------------
+def ppt_head_supported(c: int, d: int, k: int, dtype: torch.dtype) -> bool:
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    code = {torch.float32: _lib.PTC_F32, torch.float16: _lib.PTC_F16, torch.bfloat16: _lib.PTC_BF16}[dtype]
+    return bool(lib().ptc_ppt_head_supported(int(c), int(d), int(k), code))
+
+
+def _ppt_f32(t: torch.Tensor, shape, what: str, dtype=torch.float32) -> torch.Tensor:
+    require_cuda(t)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise PtcoreError(f"{what}: needs {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def ppt_head_fwd(x, w, b, e, scale: float, eps: float):
+    """-> (logits [N, K] fp32, inv_norm [N] fp32): logits = scale * (h e^T) / max(|h|, eps) with h = x w^T + b [N, D] formed and
+    consumed in registers.  x [N, C] fp32 / bf16 / fp16, w [D, C] of x's dtype, b [D] and e [K, D] (the selected class rows) fp32."""
+    require_cuda(x, w)
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1] or w.dtype != x.dtype:
+        raise PtcoreError(f"ppt_head_fwd: x {x.dtype} {tuple(x.shape)}, w {w.dtype} {tuple(w.shape)}")
+    x, w = x.contiguous(), w.contiguous()
+    (n, c), d, k = x.shape, w.shape[0], e.shape[0]
+    b, e = _ppt_f32(b, (d,), "ppt_head_fwd: b"), _ppt_f32(e, (k, d), "ppt_head_fwd: e")
+    logits = torch.empty((n, k), dtype=torch.float32, device=x.device)
+    inv = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(lib().ptc_ppt_head_fwd(ptr(x), ptr(w), ptr(b), ptr(e), n, c, d, k, dtype_code(x), float(scale), float(eps), ptr(logits), ptr(inv),
+                                 stream_ptr()), "ptc_ppt_head_fwd")
+    return logits, inv
+
+
+def ppt_head_bwd(x, dlogits, logits, inv_norm, G, M, u, d: int, scale: float, eps: float):
+    """-> (dx [N, C] of x's dtype, A [K, C], Bm [C, C], v [C], asum [K], rsum [1]) of ppt_head_fwd from dlogits [N, K] and the small
+    products G = e w [K, C] (fp32), M = w^T w [C, C], u = w^T b [C] (float64); the five reductions in a fixed order (csrc/ppt.hip)"""
+    require_cuda(x)
+    x = x.contiguous()
+    n, c = x.shape
+    k = logits.shape[1]
+    dl = _ppt_f32(dlogits, (n, k), "ppt_head_bwd: dlogits")            # kept in names: the copies must outlive the call
+    lg, iv = _ppt_f32(logits, (n, k), "ppt_head_bwd: logits"), _ppt_f32(inv_norm, (n,), "ppt_head_bwd: inv_norm")
+    G = _ppt_f32(G, (k, c), "ppt_head_bwd: G")
+    M, u = _ppt_f32(M, (c, c), "ppt_head_bwd: M", torch.float64), _ppt_f32(u, (c,), "ppt_head_bwd: u", torch.float64)
+    dev = x.device
+    dx = torch.empty_like(x)
+    A, Bm = torch.empty((k, c), dtype=torch.float32, device=dev), torch.empty((c, c), dtype=torch.float32, device=dev)
+    v, asum, rsum = (torch.empty(s, dtype=torch.float32, device=dev) for s in (c, k, 1))
+    nbytes = lib().ptc_ppt_head_workspace_bytes(n, c, int(d), k)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_ppt_head_bwd(ptr(x), ptr(dl), ptr(lg), ptr(iv), ptr(G), ptr(M), ptr(u), n, c, int(d), k, dtype_code(x), float(scale), float(eps),
+                                 ptr(dx), ptr(A), ptr(Bm), ptr(v), ptr(asum), ptr(rsum), ptr(ws), nbytes, stream_ptr()), "ptc_ppt_head_bwd")
+    return dx, A, Bm, v, asum, rsum
+
+
+# ------------------------------------------------------------------------------------------------
 # SGIFormer decoder (csrc/sgiformer.hip): ragged masked attention, mask bit-pack, matcher cost, target builder
 # ------------------------------------------------------------------------------------------------
 def sgi_attn_supported(d: int) -> bool:

@@ -118,7 +118,12 @@ class SpUNetBase(nn.Module):
         with PNN.batched_bn_counters():          # the 59 `num_batches_tracked += 1` of a training step in one launch
             return self._forward(input_dict)
 
-    def _forward(self, input_dict):
+    def _forward(self, input_dict, call=None):
+        """`call(module, x)` runs one stage module (default: module(x)); SpUNet-v1m3 passes its condition and context through it.
+        sparse_unet_v1m3.SpUNetV1m3 builds its own stages without SpUNetBase.__init__ and runs THIS method: everything read from `self`
+        here -- skip, enc_mode, num_stages, conv_input, down, enc, up, dec, final -- must be set there as well."""
+        if call is None:
+            call = lambda m, t: m(t)      # noqa: E731
         grid_coord, feat, offset = input_dict["grid_coord"], input_dict["feat"], input_dict["offset"]
         batch = offset2batch(offset, int(feat.shape[0]))
         from . import config, ops
@@ -151,19 +156,19 @@ class SpUNetBase(nn.Module):
         x.indice_dict["__hash__"] = table
         spconv.mark_duplicates(x, host[3] > 0)   # Mix3D batches: the conv backward needs to know (functional._SparseConv)
         spconv.prefetch_down_rulebooks(x, [f"spconv{s + 1}" for s in range(self.num_stages)])   # all host waits up front
-        x = self.conv_input(x)
+        x = call(self.conv_input, x)
         skips = [x]
         for s in range(self.num_stages):
-            x = self.down[s](x)
-            x = self.enc[s](x)
+            x = call(self.down[s], x)
+            x = call(self.enc[s], x)
             skips.append(x)
         x = skips.pop(-1)
         if not self.enc_mode:
             for s in reversed(range(self.num_stages)):
-                x = self.up[s](x)
+                x = call(self.up[s], x)
                 if self.skip:
                     x = x.replace_feature(torch.cat((x.features, skips.pop(-1).features), dim=1))
-                x = self.dec[s](x)
+                x = call(self.dec[s], x)
         x = self.final(x)
         if self.enc_mode:  # per-scene mean (torch_geometric.utils.scatter(reduce="mean"), :276-279)
             idx = x.indices[:, 0].long()
