@@ -1031,6 +1031,33 @@ int ptc_sonata_distill_bwd(const void* teacher, int tdtype, int64_t nt, const vo
                            const float* c, const float* lse, const float* roww, const float* dloss, int max_groups, void* dpred,
                            ptc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Concerto-v1m1 2D-3D alignment branch (csrc/concerto.hip; pointcept/models/concerto/concerto_v1m1_base.py:528-573, :745-866).
+ * ptc_concerto_pool_corr: pool_corr for one pooling level and all v images.  corr [n,v,2] (ctype 0 = fp32, 1 = int32, 2 = int64),
+ *   perm [.] = the points sorted by cluster (NULL: identity), idx_ptr [m+1]; out [m,v,2] fp32.  Per (cluster, image): count = members
+ *   with BOTH components != -1; each component summed over ALL members with -1 read as 0 (double, member order of the CSR);
+ *   out = sum / count, or (-1, -1) where count == 0.
+ * ptc_concerto_pair_keys: keys [ns*v] int64 for the pairs (i, view) of the selected rows (rows [ns] into corr [n,v,2] fp32, NULL:
+ *   identity; scene [ns]; img_offset / img_num [nb]).  A pair with any component != -1 whose truncated (row, col) lies in
+ *   [0,patch_h) x [0,patch_w) and whose view < img_num[scene] gets (img_offset[scene] + view) * patch_h * patch_w + row * patch_w + col;
+ *   every other pair gets `sentinel`.
+ * ptc_concerto_patch_mean_bwd: dfeat[rows[i]] (or row i) = sum over view of dmean[q] / (indptr[q+1] - indptr[q]), q = pair_patch[i,view]
+ *   in [0,u) (anything else: no patch); rows the list does not name are left untouched.  dmean [u,c], dfeat [n_out,c], one dtype.
+ * ptc_concerto_align: row[i] = 1 - cos(x[ids[i]] (- its mean), y[i] (- its mean)) over d <= 2048 channels with ATen's per-operand
+ *   eps clamp, loss[0] = 10 * mean(row) summed in a fixed order, and with dy != NULL dy [u,d] (y's dtype) = d loss / d y.  x [nx,d]
+ *   and y [u,d] in fp32, fp16 or bf16 independently; an id outside [0,nx) contributes 0 and gets a zero gradient.  u >= 1.
+ * ------------------------------------------------------------------------------------------ */
+int ptc_concerto_pool_corr(const void* corr, int ctype, int64_t n, int v, const int64_t* perm, const int64_t* idx_ptr, int64_t m,
+                           float* out, ptc_stream_t stream);
+int ptc_concerto_pair_keys(const float* corr, int64_t n, const int64_t* rows, const int64_t* scene, const int64_t* img_offset,
+                           const int64_t* img_num, int64_t ns, int nb, int v, int patch_h, int patch_w, int64_t sentinel,
+                           int64_t* keys, ptc_stream_t stream);
+int ptc_concerto_patch_mean_bwd(const void* dmean, int dtype, const int64_t* pair_patch, const int64_t* indptr, const int64_t* rows,
+                                int64_t ns, int64_t n_out, int v, int c, int64_t u, void* dfeat, ptc_stream_t stream);
+int ptc_concerto_align_supported(int d);
+int ptc_concerto_align(const void* x, int xdtype, int64_t nx, const int64_t* ids, const void* y, int ydtype, int64_t u, int d,
+                       int shift, double eps, float* row, float* loss, void* dy, ptc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,12 @@ _SIGNATURES = {
                                        ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "ptc_sonata_distill_bwd": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_int, c_i64, c_ptr, c_i64, c_int, ctypes.c_double, ctypes.c_double,
                                        c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr]),
+    "ptc_concerto_pool_corr": (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    "ptc_concerto_pair_keys": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_i64, c_ptr, c_ptr]),
+    "ptc_concerto_patch_mean_bwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr]),
+    "ptc_concerto_align_supported": (c_int, [c_int]),
+    "ptc_concerto_align": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, ctypes.c_double, c_ptr, c_ptr, c_ptr,
+                                   c_ptr]),
 }
 
 PTC_F32, PTC_F16, PTC_BF16 = 0, 1, 2

@@ -58,6 +58,7 @@ HIP_SOURCES = [
     "sgiformer.hip",
     "sonata.hip",
     "ppt.hip",
+    "concerto.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

@@ -87,6 +87,7 @@ OPT_IN_MODEL_CLASSES = {
     "PPT-v1m1": ("point_prompt_training", "PointPromptTraining"),     # point_prompt_training_v1m1_language_guided.py:18
     "PPT-v1m2": ("point_prompt_training", "PointPromptTrainingDecoupled"),   # point_prompt_training_v1m2_decoupled.py:18
     "PPT-v1m3": ("point_prompt_training", "PointPromptTrainingNeo"),  # point_prompt_training_v1m3_neo.py:23
+    "Concerto-v1m1": ("concerto", "Concerto"),                        # concerto/concerto_v1m1_base.py:82
 }
 
 
@@ -114,7 +115,7 @@ def register_models(registry, names=None, force: bool = True) -> list:
     names the reference's configs use, replacing the CUDA-library implementations (`force=True`), so that
     `MODELS.build(cfg.model.backbone)` constructs them.  Returns the names registered.  Without `names`: every name of
     MODEL_CLASSES; the OPT_IN_MODEL_CLASSES (OA-CNNs, PointGroup, MSC-v1m1 / -v1m2, CAC, SGIFormer, Sonata, SpUNet-v1m3,
-    PPT-v1m1 / -v1m2 / -v1m3) only when named.
+    PPT-v1m1 / -v1m2 / -v1m3, Concerto-v1m1) only when named.
 
         from pointcept.models.builder import MODELS
         import pointcept_amd.compat; pointcept_amd.compat.register_models(MODELS)

@@ -51,6 +51,9 @@ settings), and so a regression can be bisected without a rebuild.
   PTC_PPT=0          Point Prompt Training's language-guided head (point_prompt_training.py, functional.ppt_head) runs as the
                      reference's own expression -- proj_head, the row norm, the division and the class matmul, four passes over an
                      [N, 512] tensor that autograd keeps -- instead of csrc/ppt.hip (A/B baseline, and the CPU path of the port)
+  PTC_CONCERTO=0     Concerto's 2D-3D alignment branch (concerto.py, functional.concerto_*) runs as the reference's own expression -- the
+                     per-(level, image) pool_corr loop, a dense [all patches, C] scatter_mean, patch_proj over all of it, torch.unique,
+                     two gathers and the elementwise centred cosine -- instead of csrc/concerto.hip (A/B baseline, and the CPU path)
   PTC_FUSE_BLOCK=0   the three residual joints of a PTv3 Block run as separate LayerNorm / add / cast
                      kernels instead of the fused add_norm passes
 """
@@ -82,6 +85,7 @@ CAC_KERNELS = _flag("PTC_CAC", True)
 SGI_KERNELS = _flag("PTC_SGI", True)
 SONATA_KERNELS = _flag("PTC_SONATA", True)
 PPT_KERNELS = _flag("PTC_PPT", True)
+CONCERTO_KERNELS = _flag("PTC_CONCERTO", True)
 WGRAD_BLK = _flag("PTC_WGRAD_BLK", True)
 FUSE_BN_TAIL = _flag("PTC_FUSE_BN_TAIL", True)
 BATCH_BN_COUNTERS = _flag("PTC_BATCH_BN_COUNTERS", True)

@@ -2125,3 +2125,145 @@ def sonata_distill_torch(teacher_sim, student_sim, match_index, student_batch, t
     total = torch.zeros(scenes, dtype=loss.dtype, device=loss.device).index_add(0, index, loss)
     count = torch.bincount(index, minlength=scenes).clamp(min=1)
     return (total / count).mean()
+
+
+# ------------------------------------------------------------------------------------------------
+# Concerto-v1m1's 2D-3D alignment branch (concerto_v1m1_base.py:528-573, :745-866) on csrc/concerto.hip: the pooled
+# correspondence, the patch binning, the patch means of the 3D features and the centred cosine loss.  Each X_torch holds the
+# reference's expression, used for CPU tensors and under PTC_CONCERTO=0 (config.CONCERTO_KERNELS).
+# ------------------------------------------------------------------------------------------------
+def _concerto_use_kernels(t: torch.Tensor, use_kernels) -> bool:
+    if use_kernels is None:
+        use_kernels = config.CONCERTO_KERNELS and t.is_cuda
+    return bool(use_kernels)
+
+
+def _segment_sum_sorted(src: torch.Tensor, idx_ptr: torch.Tensor) -> torch.Tensor:
+    """torch_scatter.segment_csr(src, idx_ptr, reduce="sum") over dim 0"""
+    m = idx_ptr.numel() - 1
+    seg = torch.repeat_interleave(torch.arange(m, device=src.device), idx_ptr[1:] - idx_ptr[:-1])
+    return torch.zeros((m,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device).index_add_(0, seg, src[: seg.numel()])
+
+
+def concerto_pool_corr_torch(corr: torch.Tensor, perm: Optional[torch.Tensor], idx_ptr: torch.Tensor) -> torch.Tensor:
+    """one level of pool_corr (:545-570) as the reference writes it, all images at once: the mask of the fully valid members summed
+    per cluster, the -1 entries zeroed one by one, the member sum divided by the count and (-1, -1) where the count is 0"""
+    m = idx_ptr.numel() - 1
+    if corr.shape[1] == 0:
+        return -torch.ones((m, 0, 2), device=corr.device)
+    indices = perm if perm is not None else torch.arange(corr.shape[0], device=corr.device)
+    ft = corr.dtype if corr.dtype == torch.float64 else torch.float32
+    mask = torch.all(corr != -1, dim=2).to(ft)
+    counts = _segment_sum_sorted(mask[indices], idx_ptr)
+    empty = counts == 0
+    counts = counts.masked_fill(empty, 100000)
+    filled = corr.clone()
+    filled[filled == -1] = 0
+    total = _segment_sum_sorted(filled[indices], idx_ptr)
+    out = total / counts.unsqueeze(-1)
+    out[empty] = -1
+    return out
+
+
+def concerto_pool_corr(corr: torch.Tensor, perm: Optional[torch.Tensor], idx_ptr: torch.Tensor, use_kernels=None) -> torch.Tensor:
+    """The point-to-pixel correspondences [N, V, 2] pooled to the M clusters of one level (perm = points sorted by cluster, idx_ptr
+    [M + 1]) -> [M, V, 2] fp32; see ops.concerto_pool_corr.  No gradient."""
+    if not _concerto_use_kernels(corr, use_kernels) or corr.dtype not in (torch.float32, torch.int32, torch.int64):
+        return concerto_pool_corr_torch(corr, perm, idx_ptr)
+    return ops.concerto_pool_corr(corr.detach(), perm, idx_ptr)
+
+
+def concerto_patch_pairs_torch(corr, scene, img_offset, img_num, total_images: int, patch_h: int, patch_w: int, rows=None):
+    """the patch binning of :786-830 in torch: valid pairs by torch.where (ascending point row, then view), their keys, torch.unique.
+    Pairs outside their image or their scene's images are left out, as in ops.concerto_patch_pairs."""
+    dev = corr.device
+    sel = corr if rows is None else corr[rows]
+    ns, v = sel.shape[0], sel.shape[1]
+    scene = scene.long()
+    r, c = sel[..., 0].long(), sel[..., 1].long()              # .long() truncates toward zero
+    view = torch.arange(v, device=dev)
+    # trunc(a) in [0, patch_h) <=> -1 < a < patch_h, on the values themselves: a NaN is outside (its .long() depends on the device)
+    inside = (sel[..., 0] > -1) & (sel[..., 0] < patch_h) & (sel[..., 1] > -1) & (sel[..., 1] < patch_w)
+    mask = torch.any(sel != -1, dim=2) & inside & (view[None] < img_num.long()[scene][:, None])
+    pi, vi = torch.where(mask)
+    keys = (img_offset.long()[scene[pi]] + vi) * patch_h * patch_w + r[pi, vi] * patch_w + c[pi, vi]
+    ids, inv, counts = torch.unique(keys, return_inverse=True, return_counts=True)
+    order = torch.argsort(inv, stable=True)
+    indptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)])
+    point = pi[order]
+    pair_patch = torch.full((ns, v), -1, dtype=torch.int64, device=dev)
+    pair_patch[pi, vi] = inv
+    return ops.ConcertoPairs(ids, indptr, point if rows is None else rows.long()[point], pair_patch, None if rows is None else rows.long())
+
+
+def concerto_patch_pairs(corr, scene, img_offset, img_num, total_images: int, patch_h: int, patch_w: int, rows=None, use_kernels=None):
+    """ops.ConcertoPairs of the (point, image) pairs of the selected rows of the pooled correspondence; see ops.concerto_patch_pairs
+    (and there for the one difference from the reference: pairs outside their image are left out)."""
+    if not _concerto_use_kernels(corr, use_kernels) or corr.dtype != torch.float32:
+        return concerto_patch_pairs_torch(corr, scene, img_offset, img_num, total_images, patch_h, patch_w, rows)
+    return ops.concerto_patch_pairs(corr, scene, img_offset, img_num, total_images, patch_h, patch_w, rows)
+
+
+class _ConcertoPatchMean(Function):
+    @staticmethod
+    def forward(ctx, feat, pairs):
+        out, _ = ops.segment_csr_fwd(feat, pairs.perm, pairs.indptr, "mean")
+        ctx.pairs, ctx.n = pairs, feat.shape[0]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        return ops.concerto_patch_mean_bwd(grad, ctx.pairs, ctx.n), None
+
+
+def concerto_patch_mean_torch(feat: torch.Tensor, pairs) -> torch.Tensor:
+    """scatter_mean(feature3d[valid_index[0]], feature_index)[unique ids] (:826-832), compact: the rows without a pair are not made"""
+    u = pairs.num_patches
+    counts = pairs.indptr[1:] - pairs.indptr[:-1]
+    seg = torch.repeat_interleave(torch.arange(u, device=feat.device), counts)
+    total = torch.zeros((u, feat.shape[1]), dtype=feat.dtype, device=feat.device).index_add(0, seg, feat[pairs.perm])
+    return total / counts.clamp(min=1).to(feat.dtype).unsqueeze(-1)
+
+
+def concerto_patch_mean(feat: torch.Tensor, pairs, use_kernels=None) -> torch.Tensor:
+    """mean3d [U, C]: row u = the mean of feat[p] over the pairs of patch u (the fused-gather CSR reduce of csrc/rows.hip); the
+    backward gathers through pairs.pair_patch: d feat[p] = sum over p's pairs of d mean3d[u] / count[u], no atomics."""
+    if not _concerto_use_kernels(feat, use_kernels) or feat.dtype == torch.float64 or pairs.num_patches == 0:
+        return concerto_patch_mean_torch(feat, pairs)
+    return _ConcertoPatchMean.apply(feat, pairs)
+
+
+class _ConcertoAlign(Function):
+    @staticmethod
+    def forward(ctx, y, feature2d, patch_ids, cos_shift, eps):
+        loss, _, dy = ops.concerto_align(feature2d, patch_ids, y, cos_shift, eps, ctx.needs_input_grad[0])
+        ctx.save_for_backward(dy)
+        return loss[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss):
+        dy, = ctx.saved_tensors
+        return dy.mul_(dloss.to(torch.float32)), None, None, None, None
+
+
+def concerto_align_loss_torch(feature2d, patch_ids, y, cos_shift: bool = True, eps: float = 1e-6):
+    """the reference's expression (:831-842): both gathers, the centring and CosineSimilarity(dim=1, eps)"""
+    x = feature2d[patch_ids]
+    if cos_shift:
+        x = x - x.mean(dim=-1, keepdim=True)
+        y = y - y.mean(dim=-1, keepdim=True)
+    return (1 - torch.nn.CosineSimilarity(dim=1, eps=eps)(x, y)).mean() * 10
+
+
+def concerto_align_loss(feature2d, patch_ids, y, cos_shift: bool = True, eps: float = 1e-6, use_kernels=None):
+    """10 * mean_u (1 - cos(feature2d[patch_ids[u]], y[u])), both rows centred over the channels when cos_shift: an fp32 scalar,
+    differentiable in y (the gradient has y's dtype), feature2d read through the index and never copied.  The cosine is ATen's:
+    each norm clamped at eps on its own, the clamp passing the gradient from eps upwards.  No patches: the reference's mean over
+    nothing (NaN), without a launch."""
+    if (not _concerto_use_kernels(y, use_kernels) or y.dtype == torch.float64 or feature2d.dtype == torch.float64 or y.dim() != 2
+            or patch_ids.numel() == 0 or not ops.concerto_align_supported(y.shape[1])):
+        return concerto_align_loss_torch(feature2d, patch_ids, y, cos_shift, eps)
+    with torch.autocast(device_type=y.device.type, enabled=False):
+        return _ConcertoAlign.apply(y, feature2d.detach(), patch_ids, bool(cos_shift), float(eps))

@@ -2359,3 +2359,135 @@ def sonata_patch_rank(grid_coord: torch.Tensor, batch: torch.Tensor, n_batch: in
     check(lib().ptc_pool_maps_count(ptr(key), ptr(order0), n, 0, ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr()), "ptc_pool_maps_count")
     bad = ((gl.amax() >> cb) != 0) | (gl.amin() < 0) if n else ncl.new_zeros(())
     return cluster, torch.stack([ncl[0], bad.to(torch.int64)])
+
+
+# ------------------------------------------------------------------------------------------------
+# Concerto-v1m1 2D-3D alignment branch (csrc/concerto.hip)
+# ------------------------------------------------------------------------------------------------
+_CONCERTO_CORR_TYPES = {torch.float32: 0, torch.int32: 1, torch.int64: 2}
+
+
+def concerto_pool_corr(corr: torch.Tensor, perm: Optional[torch.Tensor], idx_ptr: torch.Tensor) -> torch.Tensor:
+    """Concerto.pool_corr (concerto_v1m1_base.py:545-570) for one pooling level and all images in one launch: corr [N, V, 2] (fp32,
+    int32 or int64), perm = the points sorted by cluster, idx_ptr [M + 1] -> [M, V, 2] fp32.  Per (cluster, image): sum over all
+    members with -1 read as 0, component by component, divided by the number of members with both components != -1; (-1, -1) where
+    that number is 0.  Members are summed in CSR order in double.  V == 0: an empty [M, 0, 2], no launch."""
+    require_cuda(corr, perm, idx_ptr)
+    if corr.dim() != 3 or corr.shape[2] != 2 or corr.dtype not in _CONCERTO_CORR_TYPES:
+        raise PtcoreError(f"concerto_pool_corr: correspondence must be [N, V, 2] in fp32, int32 or int64, got {tuple(corr.shape)} {corr.dtype}")
+    n, v = corr.shape[0], corr.shape[1]
+    m = idx_ptr.numel() - 1
+    out = torch.empty((m, v, 2), dtype=torch.float32, device=corr.device)
+    if m == 0 or v == 0:
+        return out
+    corr = corr.contiguous()
+    idx_ptr = idx_ptr.to(torch.int64).contiguous()
+    perm = None if perm is None else perm.to(torch.int64).contiguous()
+    if perm is not None and perm.numel() < n:
+        raise PtcoreError("concerto_pool_corr: perm is shorter than the points")
+    check(lib().ptc_concerto_pool_corr(ptr(corr), _CONCERTO_CORR_TYPES[corr.dtype], n, v, ptr(perm), ptr(idx_ptr), m, ptr(out), stream_ptr()),
+          "ptc_concerto_pool_corr")
+    return out
+
+
+class ConcertoPairs:
+    """The (point, image) pairs of the alignment branch grouped by image patch: patch_ids [U] (sorted unique), indptr [U + 1] over the
+    pairs in (patch, point row, view) order, perm [P] = the feature row of every pair in that order, pair_patch [Ns, V] = the patch
+    (index into patch_ids) of every pair or -1, rows [Ns] = the feature row of every selected point (None: identity)."""
+
+    def __init__(self, patch_ids, indptr, perm, pair_patch, rows):
+        self.patch_ids, self.indptr, self.perm, self.pair_patch, self.rows = patch_ids, indptr, perm, pair_patch, rows
+
+    @property
+    def num_patches(self) -> int:
+        return int(self.patch_ids.numel())
+
+    @property
+    def num_pairs(self) -> int:
+        return int(self.perm.numel())
+
+
+def concerto_patch_pairs(corr: torch.Tensor, scene: torch.Tensor, img_offset: torch.Tensor, img_num: torch.Tensor, total_images: int,
+                         patch_h: int, patch_w: int, rows: Optional[torch.Tensor] = None) -> ConcertoPairs:
+    """The patch binning of :786-830 without the dense tensor.  corr [N, V, 2] fp32 pooled correspondence, rows [Ns] the selected
+    points (None: all), scene [Ns] their scene, img_offset / img_num [B] the first image and the image count of every scene,
+    total_images = img_num.sum() (host).  A pair (point, view) with any(corr != -1) gets the key
+    (img_offset[scene] + view) * patch_h * patch_w + trunc(row) * patch_w + trunc(col); one key sort (ops.sort_keys) and the
+    run-numbering kernels of the pooling maps give the sorted unique ids -- torch.unique's order -- and the CSR, pairs inside a patch
+    by ascending point row, then view.  One host read (the number of patches and of pairs).
+    DIFFERENCE FROM THE REFERENCE: a pair whose truncated row or column lies outside [0, patch_h) x [0, patch_w), or whose view is at
+    or beyond its scene's img_num, aliases into another image's patches there; here it is left out."""
+    require_cuda(corr, scene, img_offset, img_num, rows)
+    if corr.dim() != 3 or corr.shape[2] != 2 or corr.dtype != torch.float32:
+        raise PtcoreError(f"concerto_patch_pairs: pooled correspondence must be [N, V, 2] fp32, got {tuple(corr.shape)} {corr.dtype}")
+    dev = corr.device
+    n, v = corr.shape[0], corr.shape[1]
+    rows = None if rows is None else rows.to(torch.int64).contiguous()
+    ns = n if rows is None else rows.numel()
+    if scene.numel() != ns:
+        raise PtcoreError("concerto_patch_pairs: one scene per selected row")
+    e = ns * v
+    empty = torch.empty(0, dtype=torch.int64, device=dev)
+    if e == 0:
+        return ConcertoPairs(empty, torch.zeros(1, dtype=torch.int64, device=dev), empty, torch.full((ns, v), -1, dtype=torch.int64, device=dev), rows)
+    sentinel = max(int(total_images), 0) * int(patch_h) * int(patch_w)
+    keys = torch.empty(e, dtype=torch.int64, device=dev)
+    check(lib().ptc_concerto_pair_keys(ptr(corr.contiguous()), n, ptr(rows), ptr(scene.to(torch.int64).contiguous()),
+                                       ptr(img_offset.to(torch.int64).contiguous()), ptr(img_num.to(torch.int64).contiguous()), ns,
+                                       img_num.numel(), v, int(patch_h), int(patch_w), sentinel, ptr(keys), stream_ptr()), "ptc_concerto_pair_keys")
+    order, _ = sort_keys(keys[None].contiguous(), 0, max(1, sentinel.bit_length()), want_inverse=False)
+    order0 = order[0].contiguous()
+    cluster = torch.empty(e, dtype=torch.int64, device=dev)
+    ncl = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = lib().ptc_pool_maps_workspace_bytes(e)
+    ws = _ws(nbytes, dev)
+    check(lib().ptc_pool_maps_count(ptr(keys), ptr(order0), e, 0, ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr()), "ptc_pool_maps_count")
+    live = keys != sentinel
+    n_cluster, n_pairs = torch.stack([ncl[0], live.sum()]).tolist()
+    u = n_cluster - (1 if n_pairs < e else 0)          # the sentinel, where present, is the last run
+    idx_ptr = torch.empty(n_cluster + 1, dtype=torch.int64, device=dev)
+    head = torch.empty(n_cluster, dtype=torch.int64, device=dev)
+    check(lib().ptc_pool_maps_fill(ptr(order0), ptr(cluster), e, n_cluster, ptr(idx_ptr), ptr(head), stream_ptr()), "ptc_pool_maps_fill")
+    point = torch.div(order0[:n_pairs], v, rounding_mode="floor")
+    perm = point if rows is None else rows[point]
+    pair_patch = torch.where(live, cluster, torch.full_like(cluster, -1)).view(ns, v)
+    return ConcertoPairs(keys[head[:u]], idx_ptr[:u + 1].contiguous(), perm.contiguous(), pair_patch, rows)
+
+
+def concerto_patch_mean_bwd(dmean: torch.Tensor, pairs: ConcertoPairs, n_out: int) -> torch.Tensor:
+    """d feat3d [n_out, C] from d mean3d [U, C]: row p = sum over p's pairs of d mean3d[u] / count[u], gathered through
+    pairs.pair_patch (no atomics); rows outside the selection are zero."""
+    require_cuda(dmean)
+    dmean = dmean.contiguous()
+    u, c = dmean.shape
+    ns, v = pairs.pair_patch.shape
+    alloc = torch.empty if pairs.rows is None else torch.zeros
+    out = alloc((int(n_out), c), dtype=dmean.dtype, device=dmean.device)
+    check(lib().ptc_concerto_patch_mean_bwd(ptr(dmean), dtype_code(dmean), ptr(pairs.pair_patch.contiguous()), ptr(pairs.indptr), ptr(pairs.rows),
+                                            ns, int(n_out), v, c, u, ptr(out), stream_ptr()), "ptc_concerto_patch_mean_bwd")
+    return out
+
+
+def concerto_align_supported(d: int) -> bool:
+    """the centred-cosine kernel keeps a row in one wave's registers: up to 2048 channels"""
+    return bool(lib().ptc_concerto_align_supported(int(d)))
+
+
+def concerto_align(feature2d: torch.Tensor, patch_ids: torch.Tensor, y: torch.Tensor, cos_shift: bool, eps: float, want_dy: bool):
+    """-> (loss [1] fp32 = 10 * mean_u (1 - cos(feature2d[patch_ids[u]], y[u])), row [U] fp32 = 1 - cos, dy [U, D] in y's dtype or
+    None); with cos_shift both rows are centred over D first.  feature2d and y in fp32, bf16 or fp16 independently."""
+    require_cuda(feature2d, patch_ids, y)
+    ok = (torch.float32, torch.bfloat16, torch.float16)
+    if feature2d.dim() != 2 or y.dim() != 2 or feature2d.shape[1] != y.shape[1] or feature2d.dtype not in ok or y.dtype not in ok:
+        raise PtcoreError(f"concerto_align: feature2d {tuple(feature2d.shape)} {feature2d.dtype}, y {tuple(y.shape)} {y.dtype}")
+    u, d = y.shape
+    if patch_ids.numel() != u or u < 1 or not concerto_align_supported(d):
+        raise PtcoreError(f"concerto_align: {patch_ids.numel()} ids for {u} rows (at least one) of {d} channels (at most 2048)")
+    x, yy = feature2d.detach().contiguous(), y.detach().contiguous()
+    ids = patch_ids.to(torch.int64).contiguous()
+    row = torch.empty(u, dtype=torch.float32, device=y.device)
+    loss = torch.empty(1, dtype=torch.float32, device=y.device)
+    dy = torch.empty_like(yy) if want_dy else None
+    check(lib().ptc_concerto_align(ptr(x), dtype_code(x), x.shape[0], ptr(ids), ptr(yy), dtype_code(yy), u, d, int(bool(cos_shift)), float(eps),
+                                   ptr(row), ptr(loss), ptr(dy), stream_ptr()), "ptc_concerto_align")
+    return loss, row, dy

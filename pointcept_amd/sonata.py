@@ -73,11 +73,13 @@ class CosineScheduler:
 
 class OnlineCluster(nn.Module):
     """:27-68: Linear, GELU, Linear, L2 normalisation, a weight-normed prototype layer whose magnitudes are frozen at 1 -- the
-    output is the cosine similarity to each prototype"""
+    output is the cosine similarity to each prototype.  enable_mlp=False (Concerto's concerto_v1m1_base.py:41-49) leaves the MLP out:
+    the input is normalised and meets the prototypes directly."""
 
-    def __init__(self, in_channels, hidden_channels=4096, embed_channels=512, num_prototypes=4096):
+    def __init__(self, in_channels, hidden_channels=4096, embed_channels=512, num_prototypes=4096, enable_mlp=True):
         super().__init__()
-        self.mlp = nn.Sequential(nn.Linear(in_channels, hidden_channels), nn.GELU(), nn.Linear(hidden_channels, embed_channels))
+        if enable_mlp:
+            self.mlp = nn.Sequential(nn.Linear(in_channels, hidden_channels), nn.GELU(), nn.Linear(hidden_channels, embed_channels))
         self.apply(self._init_weights)
         self.prototype = torch.nn.utils.parametrizations.weight_norm(nn.Linear(embed_channels, num_prototypes, bias=False))
         self.prototype.parametrizations.weight.original0.data.fill_(1)
@@ -91,7 +93,8 @@ class OnlineCluster(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def forward(self, feat):
-        feat = self.mlp(feat)
+        if hasattr(self, "mlp"):
+            feat = self.mlp(feat)
         eps = 1e-6 if feat.dtype == torch.float16 else 1e-12
         feat = nn.functional.normalize(feat, dim=-1, p=2, eps=eps)
         return self.prototype(feat)

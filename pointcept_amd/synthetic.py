@@ -320,3 +320,65 @@ def multi_view_batch(seeds, global_size: int, local_size: int, grid: float = 0.0
         out[f"{group}_offset"] = np.cumsum([v.shape[0] for v in coord]).astype(np.int64)
     out["grid_size"] = np.full(len(seeds), grid, np.float32)
     return out
+
+
+def multi_view_image_batch(seeds, global_size: int, local_size: int, img_nums, patch_h: int, patch_w: int, patch_size: float = 0.16,
+                           pixels_per_patch: int = 2, grid: float = 0.02, **kw):
+    """multi_view_batch plus what Concerto's forward reads for its 2D-3D term, in collated form:
+    global_correspondence [points of the global views, max(img_nums), 2] int64 -- the image patch (row, col) each point projects to in
+    every image of its scene, -1 where it falls outside the image and in the padded views of a scene with fewer images --, images
+    [sum(img_nums), 3, patch_h * pixels_per_patch, patch_w * pixels_per_patch] float32 and img_num [scenes] int64.  Image v of a
+    scene looks straight down at the scene's first global view: a rotation about z, a shift of up to a third of the patch grid and a
+    patch edge of patch_size metres of the scene (origin_coord), so that neighbouring points share a patch and part of every view
+    lies outside every image."""
+    out = multi_view_batch(seeds, global_size, local_size, grid=grid, **kw)
+    img_nums = [int(v) for v in img_nums]
+    assert len(img_nums) == len(seeds)
+    rng = np.random.default_rng(int(seeds[0]) * 104729 + 7)
+    offset = np.concatenate([[0], out["global_offset"]])
+    views_per_scene = (len(offset) - 1) // len(seeds)
+    vmax = max(img_nums) if img_nums else 0
+    corr = np.full((int(offset[-1]), vmax, 2), -1, np.int64)
+    for b, n_img in enumerate(img_nums):
+        lo, hi = int(offset[b * views_per_scene]), int(offset[(b + 1) * views_per_scene])
+        first = out["global_origin_coord"][lo:int(offset[b * views_per_scene + 1])]
+        centre = np.median(first[:, :2], 0)
+        xy = out["global_origin_coord"][lo:hi, :2] - centre
+        for v in range(n_img):
+            a = rng.uniform(0, 2 * np.pi)
+            rot = np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+            shift = rng.uniform(-1 / 3, 1 / 3, 2) * np.array([patch_h, patch_w])
+            rc = np.floor((xy @ rot.T) / patch_size + np.array([patch_h, patch_w]) / 2 + shift).astype(np.int64)
+            inside = (rc[:, 0] >= 0) & (rc[:, 0] < patch_h) & (rc[:, 1] >= 0) & (rc[:, 1] < patch_w)
+            corr[lo:hi, v][inside] = rc[inside]
+    out["global_correspondence"] = corr
+    out["images"] = rng.uniform(-1, 1, (sum(img_nums), 3, patch_h * pixels_per_patch, patch_w * pixels_per_patch)).astype(np.float32)
+    out["img_num"] = np.asarray(img_nums, np.int64)
+    return out
+
+
+def stand_in_image_encoder(patch_h: int, patch_w: int, channels: int, num_register_tokens: int = 5):
+    """A small deterministic stand-in for the frozen image encoder of Concerto (no download, no random initialisation): every image
+    patch is averaged over its pixels, mapped to `channels` by a fixed sinusoidal matrix and given a fixed positional term; the result
+    is an object with last_hidden_state [images, num_register_tokens + patch_h * patch_w, channels], the register / class tokens in
+    FRONT as in the DINOv2 family (Concerto.ENC2D_forward takes the last patch_h * patch_w tokens)."""
+    import types
+
+    import torch
+
+    class StandInImageEncoder(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            c = torch.arange(channels, dtype=torch.float64)
+            p = torch.arange(patch_h * patch_w, dtype=torch.float64)
+            self.proj = torch.nn.Parameter(torch.stack([torch.sin(0.37 * (k + 1) * (c + 1)) for k in range(3)]).float())
+            self.pos = torch.nn.Parameter((0.5 * torch.cos(0.11 * (p[:, None] + 1) * (c[None] + 2) % 6.283)).float())
+            self.register = torch.nn.Parameter(torch.cos(0.23 * (torch.arange(num_register_tokens, dtype=torch.float64)[:, None] + 1) * (c[None] + 1)).float())
+
+        def forward(self, x):
+            pooled = torch.nn.functional.adaptive_avg_pool2d(x.to(self.proj.dtype), (patch_h, patch_w))       # [I, 3, ph, pw]
+            tokens = pooled.flatten(2).transpose(1, 2) @ self.proj + self.pos                                # [I, ph * pw, C]
+            tokens = torch.cat([self.register[None].expand(x.shape[0], -1, -1), tokens], dim=1)
+            return types.SimpleNamespace(last_hidden_state=tokens)
+
+    return StandInImageEncoder().eval()
