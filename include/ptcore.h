@@ -1058,6 +1058,36 @@ int ptc_concerto_align_supported(int d);
 int ptc_concerto_align(const void* x, int xdtype, int64_t nx, const int64_t* ids, const void* y, int ydtype, int64_t u, int d,
                        int shift, double eps, float* row, float* loss, void* dy, ptc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A criteria list of row-local segmentation losses in one pass per direction (csrc/criteria.hip; pointcept/models/losses/misc.py).
+ * `flags` selects the terms: 1 = CrossEntropyLoss(weight, label_smoothing, reduction mean | sum), 2 = FocalLoss(gamma, alpha, mean),
+ *   4 = DiceLoss(smooth, exponent 1 | 2 | 3); all share ignore_index.  logits [n,c] (fp32 / fp16 / bf16, row stride >= c), target [n]
+ *   int64.  c <= 32: any combination; 32 < c <= 1024: flags == 1 only.  A row is counted iff target != ignore_index && 0 <= target < c;
+ *   the Dice term takes every row with target != ignore_index and clamps its label into [0, c-1], as the reference does.
+ *   ce_weight / focal_alpha_vec: [c] fp32 on the device, or NULL (all ones / the scalar focal_alpha).
+ * ptc_criteria_partials(n) rows of ptc_criteria_partial_width(c, flags) floats: the per-workgroup partial sums.
+ * ptc_criteria_fwd: lsum [n] = log sum_j exp(x_j - max_j x_j) (the backward recomputes the maximum) and partial [rows, width]: columns 0-3 = CE loss sum, CE denominator (sum of weight[target]), focal sum,
+ *   focal counted rows; with flag 4, then A[c] = sum p[target], B[c] = sum p^exponent, T[c] = label count.  No atomics: every sum has a
+ *   fixed order.  The caller sums the partial rows (in double, fixed order) into sums [width].
+ * ptc_criteria_finish: sums -> out [4] fp32 = (total, ce, focal, dice), each term times its loss_weight (mean CE over a zero denominator
+ *   is nan, as ATen; focal over no counted row is 0), and coef [4 + 2c] fp32 = (CE scale, focal scale, sum of weights, dice_loss_weight,
+ *   2 / (c den_k), exponent num_k / (c den_k^2)) for the backward.  Nothing is read back by the host.
+ * ptc_criteria_bwd: dlogits [n,c] dense, logits' dtype = gscale[0] * d total / d logits (gscale: device scalar fp32); the arguments
+ *   that describe the terms must be those of the forward.
+ * ------------------------------------------------------------------------------------------ */
+int64_t ptc_criteria_partials(int64_t n);
+int64_t ptc_criteria_partial_width(int c, int flags);
+int ptc_criteria_fwd(const void* logits, int64_t row_stride, const int64_t* target, int64_t n, int c, int dtype, int64_t ignore_index,
+                     int flags, const float* ce_weight, double label_smoothing, const float* focal_alpha_vec, double focal_alpha,
+                     double focal_gamma, int dice_exponent, float* lsum, float* partial, ptc_stream_t stream);
+int ptc_criteria_finish(const double* sums, int c, int flags, int64_t ignore_index, const float* ce_weight, int ce_reduction_sum,
+                        double ce_loss_weight, double focal_loss_weight, double dice_loss_weight, double dice_smooth, int dice_exponent,
+                        float* out, float* coef, ptc_stream_t stream);
+int ptc_criteria_bwd(const void* logits, int64_t row_stride, const int64_t* target, const float* lsum, const float* coef,
+                     const float* gscale, int64_t n, int c, int dtype, int64_t ignore_index, int flags, const float* ce_weight,
+                     double label_smoothing, const float* focal_alpha_vec, double focal_alpha, double focal_gamma, int dice_exponent,
+                     void* dlogits, ptc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

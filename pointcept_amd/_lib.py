@@ -226,6 +226,14 @@ _SIGNATURES = {
     "ptc_concerto_align_supported": (c_int, [c_int]),
     "ptc_concerto_align": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, ctypes.c_double, c_ptr, c_ptr, c_ptr,
                                    c_ptr]),
+    "ptc_criteria_partials": (c_i64, [c_i64]),
+    "ptc_criteria_partial_width": (c_i64, [c_int, c_int]),
+    "ptc_criteria_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_int, c_ptr, ctypes.c_double, c_ptr, ctypes.c_double,
+                                 ctypes.c_double, c_int, c_ptr, c_ptr, c_ptr]),
+    "ptc_criteria_finish": (c_int, [c_ptr, c_int, c_int, c_i64, c_ptr, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, c_int, c_ptr, c_ptr, c_ptr]),
+    "ptc_criteria_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_i64, c_int, c_ptr, ctypes.c_double,
+                                 c_ptr, ctypes.c_double, ctypes.c_double, c_int, c_ptr, c_ptr]),
 }
 
 PTC_F32, PTC_F16, PTC_BF16 = 0, 1, 2

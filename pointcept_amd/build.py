@@ -59,6 +59,7 @@ HIP_SOURCES = [
     "sonata.hip",
     "ppt.hip",
     "concerto.hip",
+    "criteria.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

@@ -54,6 +54,10 @@ settings), and so a regression can be bisected without a rebuild.
   PTC_CONCERTO=0     Concerto's 2D-3D alignment branch (concerto.py, functional.concerto_*) runs as the reference's own expression -- the
                      per-(level, image) pool_corr loop, a dense [all patches, C] scatter_mean, patch_proj over all of it, torch.unique,
                      two gathers and the elementwise centred cosine -- instead of csrc/concerto.hip (A/B baseline, and the CPU path)
+  PTC_CRITERIA=0     the criteria terms of csrc/criteria.hip (functional.seg_criteria: class-weighted / label-smoothed / summed
+                     CrossEntropyLoss, FocalLoss, DiceLoss; criteria.Criteria) run as their torch twins -- the reference's own
+                     expressions, several fp32 [N, C] temporaries per term and direction -- instead of one fused pass per direction
+                     (A/B baseline, and the CPU path); the default CrossEntropyLoss and LovaszLoss keep their kernels either way
   PTC_FUSE_BLOCK=0   the three residual joints of a PTv3 Block run as separate LayerNorm / add / cast
                      kernels instead of the fused add_norm passes
 """
@@ -86,6 +90,7 @@ SGI_KERNELS = _flag("PTC_SGI", True)
 SONATA_KERNELS = _flag("PTC_SONATA", True)
 PPT_KERNELS = _flag("PTC_PPT", True)
 CONCERTO_KERNELS = _flag("PTC_CONCERTO", True)
+CRITERIA_KERNELS = _flag("PTC_CRITERIA", True)
 WGRAD_BLK = _flag("PTC_WGRAD_BLK", True)
 FUSE_BN_TAIL = _flag("PTC_FUSE_BN_TAIL", True)
 BATCH_BN_COUNTERS = _flag("PTC_BATCH_BN_COUNTERS", True)

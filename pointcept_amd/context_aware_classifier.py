@@ -54,7 +54,7 @@ class CACSegmentor(nn.Module):
         self.proj = nn.Sequential(PNN.Linear(c * 2, c * 2, bias=False), PNN.ReLU(), PNN.Linear(c * 2, c))
         self.apd_proj = nn.Sequential(PNN.Linear(c * 2, c * 2, bias=False), PNN.ReLU(), PNN.Linear(c * 2, c))
         self.feat_proj_layer = nn.Sequential(PNN.Linear(c, c, bias=False), PNN.BatchNorm1d(c), PNN.ReLU(), PNN.Linear(c, c))
-        self.criteria = criteria if callable(criteria) else Criteria(criteria, "CAC-v1m1")
+        self.criteria = criteria if callable(criteria) else Criteria(criteria, "CAC-v1m1", row_terms=False)
         self.last = {}               # integers of the last forward (rows past the gate per scene, class counts), for tests and tools
 
     def _kernels(self, feat: torch.Tensor) -> bool:

@@ -778,13 +778,228 @@ class _CrossEntropy(Function):
         return d, None, None
 
 
-def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -1) -> torch.Tensor:
+def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -1, weight=None, label_smoothing: float = 0.0,
+                  reduction: str = "mean") -> torch.Tensor:
     """nn.CrossEntropyLoss(ignore_index=ignore_index) (mean over counted points) on seg logits [N, C]
     (pointcept/models/losses/misc.py, pointcept/models/default.py:78-84): one forward and one backward
-    kernel, fp32 log-sum-exp straight from the head's (bf16, possibly strided) output."""
+    kernel, fp32 log-sum-exp straight from the head's (bf16, possibly strided) output.
+    With a class `weight` ([C] list or tensor), `label_smoothing` or reduction="sum" the call is the one-term seg_criteria (csrc/criteria.hip;
+    up to 1024 classes, element-wise above 32); with all three at their defaults it is exactly the call above."""
     if logits.dim() != 2:
         raise PtcoreError("cross_entropy expects [N, C] logits")
-    return _CrossEntropy.apply(logits, target, int(ignore_index))
+    if weight is None and float(label_smoothing) == 0.0 and reduction == "mean":
+        return _CrossEntropy.apply(logits, target, int(ignore_index))
+    return seg_criteria(logits, target, [dict(type="CrossEntropyLoss", weight=weight, label_smoothing=label_smoothing, reduction=reduction)],
+                        ignore_index)
+
+
+# ------------------------------------------------------------------------------------------------
+# criteria lists: weighted / smoothed cross entropy, Focal and Dice in one pass per direction (csrc/criteria.hip)
+# ------------------------------------------------------------------------------------------------
+CRITERIA_ROW_TERMS = {      # reference class (losses/misc.py) -> (kernel slot, settings and their defaults)
+    "CrossEntropyLoss": ("ce", dict(weight=None, size_average=None, reduce=None, reduction="mean", label_smoothing=0.0)),
+    "FocalLoss": ("focal", dict(gamma=2.0, alpha=0.5, reduction="mean")),
+    "DiceLoss": ("dice", dict(smooth=1, exponent=2)),
+}
+CRITERIA_REFUSED = {        # registered by the reference, refused here by name
+    "SmoothCELoss": "the reference's SmoothCELoss raises AttributeError (Tensor.total): there is nothing to be faithful to",
+    "BinaryFocalLoss": "BinaryFocalLoss takes [N] predictions, not [N, C] seg logits",
+}
+
+
+def criteria_terms(terms, ignore_index=None):
+    """The reference's config dicts of row-local terms (type = CrossEntropyLoss | FocalLoss | DiceLoss, loss_weight, ignore_index and
+    the class's own settings) -> ([(slot, loss_weight, settings with defaults filled)], ignore_index).  All terms of one call share one
+    ignore_index (`ignore_index` overrides the dicts'; default -1).  Refused by name (ValueError): an unknown type or setting,
+    SmoothCELoss, BinaryFocalLoss, reduction="none" (and the deprecated size_average / reduce), FocalLoss(reduction="sum") -- which
+    raises AttributeError in the reference."""
+    out, ignores = [], set()
+    for term in terms:
+        term = dict(term)
+        kind = term.pop("type")
+        lw = float(term.pop("loss_weight", 1.0))
+        if "ignore_index" in term:
+            ignores.add(int(term.pop("ignore_index")))
+        if kind in CRITERIA_REFUSED:
+            raise ValueError(f"criteria: {kind} is refused: {CRITERIA_REFUSED[kind]}")
+        if kind not in CRITERIA_ROW_TERMS:
+            raise ValueError(f"criteria: {kind} is not a row-local term of the engine's criteria kernels")
+        slot, defaults = CRITERIA_ROW_TERMS[kind]
+        unknown = sorted(set(term) - set(defaults))
+        if unknown:
+            raise ValueError(f"criteria: {kind} has no setting {unknown}")
+        s = dict(defaults, **term)
+        if slot != "dice" and s["reduction"] not in ("mean", "sum"):
+            raise ValueError(f"criteria: {kind}(reduction={s['reduction']!r}) is refused: a per-row loss has no place in a summed criteria list")
+        if slot == "ce" and (s["size_average"] is not None or s["reduce"] is not None):
+            raise ValueError(f"criteria: {kind} with the deprecated size_average / reduce is refused: say reduction=")
+        if slot == "focal":
+            if s["reduction"] == "sum":
+                raise ValueError("criteria: FocalLoss(reduction='sum') is refused: the reference raises AttributeError (Tensor.total) there")
+            if not isinstance(s["gamma"], float) or not (isinstance(s["alpha"], (float, list)) or torch.is_tensor(s["alpha"])):
+                raise ValueError("criteria: FocalLoss takes a float gamma and a float or list alpha, as the reference asserts")
+        out.append((slot, lw, s))
+    if ignore_index is None:
+        if len(ignores) > 1:
+            raise ValueError(f"criteria: one fused call shares one ignore_index, got {sorted(ignores)}")
+        ignore_index = ignores.pop() if ignores else -1
+    return out, int(ignore_index)
+
+
+def _criteria_float(x: torch.Tensor) -> torch.Tensor:
+    """the twins compute 16-bit logits in fp32 (the reference's modules run under autocast, where these ops are fp32 too)"""
+    return x.float() if x.dtype in (torch.bfloat16, torch.float16) else x
+
+
+def _criteria_vec(v, like: torch.Tensor, dtype=None):
+    return torch.as_tensor(v, dtype=dtype or like.dtype, device=like.device)
+
+
+def cross_entropy_torch(logits, target, ignore_index: int = -1, weight=None, label_smoothing: float = 0.0, reduction: str = "mean"):
+    """misc.py:38-39: nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing).  Labels outside [0, C) are not counted (the
+    kernels' rule; ATen asserts on them)."""
+    x = _criteria_float(logits)
+    t = torch.where((target < 0) | (target >= x.shape[1]), torch.full_like(target, ignore_index), target)
+    w = None if weight is None else _criteria_vec(weight, x)
+    return F.cross_entropy(x, t, weight=w, ignore_index=int(ignore_index), reduction=reduction, label_smoothing=float(label_smoothing))
+
+
+def focal_loss_torch(logits, target, gamma: float = 2.0, alpha=0.5, ignore_index: int = -1):
+    """FocalLoss(gamma, alpha, reduction="mean", ignore_index).forward (misc.py:123-172) without its loss_weight; labels outside [0, C)
+    are not counted (F.one_hot raises on them); with no counted row a zero TENSOR where the reference returns the float 0.0."""
+    pred = _criteria_float(logits)
+    valid_mask = (target != ignore_index) & (target >= 0) & (target < pred.shape[1])
+    target = target[valid_mask]
+    pred = pred[valid_mask]
+    if target.numel() == 0:
+        return pred.sum() * 0
+    target = F.one_hot(target, num_classes=pred.size(1))
+    if isinstance(alpha, list) or torch.is_tensor(alpha):
+        alpha = _criteria_vec(alpha, pred)
+    pred_sigmoid = pred.sigmoid()
+    target = target.type_as(pred)
+    one_minus_pt = (1 - pred_sigmoid) * target + pred_sigmoid * (1 - target)
+    focal_weight = (alpha * target + (1 - alpha) * (1 - target)) * one_minus_pt.pow(gamma)
+    return (F.binary_cross_entropy_with_logits(pred, target, reduction="none") * focal_weight).mean()
+
+
+def dice_loss_torch(logits, target, smooth=1, exponent=2, ignore_index: int = -1):
+    """DiceLoss(smooth, exponent, ignore_index).forward (misc.py:188-223) without its loss_weight, quirks included: labels other than
+    ignore_index are clamped into [0, C-1]; class i == ignore_index is skipped while the divisor stays C."""
+    pred = _criteria_float(logits)
+    valid_mask = target != ignore_index
+    target = target[valid_mask]
+    pred = F.softmax(pred[valid_mask], dim=1)
+    num_classes = pred.shape[1]
+    target = F.one_hot(torch.clamp(target.long(), 0, num_classes - 1), num_classes=num_classes)
+    total_loss = 0
+    for i in range(num_classes):
+        if i != ignore_index:
+            num = torch.sum(torch.mul(pred[:, i], target[:, i])) * 2 + smooth
+            den = torch.sum(pred[:, i].pow(exponent) + target[:, i].pow(exponent)) + smooth
+            total_loss = total_loss + (1 - num / den)
+    return total_loss / num_classes
+
+
+def _criteria_twin(slot, s, logits, target, ignore_index):
+    if slot == "ce":
+        return cross_entropy_torch(logits, target, ignore_index, s["weight"], s["label_smoothing"], s["reduction"])
+    if slot == "focal":
+        return focal_loss_torch(logits, target, s["gamma"], s["alpha"], ignore_index)
+    return dice_loss_torch(logits, target, s["smooth"], s["exponent"], ignore_index)
+
+
+def seg_criteria_torch(logits, target, terms, ignore_index=None):
+    """the weighted sum of the terms as the reference computes it (builder.py:22-31 over misc.py's modules)"""
+    norm, ignore = criteria_terms(terms, ignore_index)
+    loss = 0
+    for slot, lw, s in norm:
+        loss = loss + _criteria_twin(slot, s, logits, target, ignore) * lw
+    return loss
+
+
+class _SegCriteria(Function):
+    @staticmethod
+    def forward(ctx, logits, target, spec):
+        out, lse, coef = ops.criteria_rows_fwd(logits, target, spec)
+        ctx.save_for_backward(logits, target, lse, coef)
+        ctx.spec = spec
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        logits, target, lse, coef = ctx.saved_tensors
+        return ops.criteria_rows_bwd(logits, target, lse, coef, g, ctx.spec), None, None
+
+
+def _criteria_fill(spec, slot, lw, s, logits):
+    if slot == "ce":
+        spec.flags |= ops.CRITERIA_CE
+        spec.ce_weight = None if s["weight"] is None else _criteria_vec(s["weight"], logits, torch.float32).contiguous()
+        spec.ce_eps, spec.ce_sum, spec.ce_lw = float(s["label_smoothing"]), s["reduction"] == "sum", lw
+    elif slot == "focal":
+        spec.flags |= ops.CRITERIA_FOCAL
+        if isinstance(s["alpha"], list) or torch.is_tensor(s["alpha"]):
+            spec.focal_alpha_vec = _criteria_vec(s["alpha"], logits, torch.float32).contiguous()
+        else:
+            spec.focal_alpha = float(s["alpha"])
+        spec.focal_gamma, spec.focal_lw = float(s["gamma"]), lw
+    else:
+        spec.flags |= ops.CRITERIA_DICE
+        spec.dice_smooth, spec.dice_exp, spec.dice_lw = float(s["smooth"]), int(s["exponent"]), lw
+
+
+def seg_criteria(logits: torch.Tensor, target: torch.Tensor, terms, ignore_index=None, use_kernels=None) -> torch.Tensor:
+    """The weighted sum of a list of row-local criteria on seg logits [N, C] -- `terms` are the reference's config dicts, see
+    criteria_terms -- as ONE autograd Function on csrc/criteria.hip: one forward and one backward kernel read the logits once and write
+    dlogits once for the whole list (class-weighted / label-smoothed CrossEntropyLoss with reduction mean | sum, FocalLoss, DiceLoss);
+    the means' denominators and Dice's per-class sums stay on the device (no host read), no atomics (bit-reproducible).  A list
+    that names one class twice takes one more call for the second instance.
+    Kernels: fp32 / bf16 / fp16 logits (any row stride) of up to 32 classes.  The torch twins (*_torch, the reference's expressions)
+    serve: FocalLoss and DiceLoss above 32 classes (CrossEntropyLoss stays on the element-wise kernels up to 1024), a DiceLoss exponent
+    other than 1 / 2 / 3, float64 logits, CPU tensors, and everything under PTC_CRITERIA=0 (config.CRITERIA_KERNELS).
+    Stated difference: FocalLoss with no counted row gives a zero tensor (zero gradient), where the reference returns the float 0.0."""
+    if logits.dim() != 2:
+        raise PtcoreError("seg_criteria expects [N, C] logits")
+    norm, ignore = criteria_terms(terms, ignore_index)
+    if use_kernels is None:
+        use_kernels = config.CRITERIA_KERNELS and logits.is_cuda
+    c = logits.shape[1]
+    specs, twins = [], []
+    for slot, lw, s in norm:
+        on_kernel = (use_kernels and logits.dtype in (torch.float32, torch.bfloat16, torch.float16)
+                     and (c <= ops.CRITERIA_ROWS_MAX_C or (slot == "ce" and c <= ops.CRITERIA_CE_MAX_C))
+                     and (slot != "dice" or s["exponent"] in (1, 2, 3)))
+        if not on_kernel:
+            twins.append((slot, lw, s))
+            continue
+        bit = {"ce": ops.CRITERIA_CE, "focal": ops.CRITERIA_FOCAL, "dice": ops.CRITERIA_DICE}[slot]
+        spec = next((sp for sp in specs if not sp.flags & bit), None)
+        if spec is None:
+            spec = ops.CriteriaSpec(ignore)
+            specs.append(spec)
+        _criteria_fill(spec, slot, lw, s, logits)
+    loss = None
+    for spec in specs:
+        term = _SegCriteria.apply(logits, target, spec)
+        loss = term if loss is None else loss + term
+    for slot, lw, s in twins:
+        term = _criteria_twin(slot, s, logits, target, ignore) * lw
+        loss = term if loss is None else loss + term
+    return loss if loss is not None else logits.sum() * 0
+
+
+def focal_loss(logits, target, gamma: float = 2.0, alpha=0.5, ignore_index: int = -1, use_kernels=None) -> torch.Tensor:
+    """FocalLoss(gamma, alpha float | list[C], reduction="mean", ignore_index) (misc.py:96-172) as the one-term seg_criteria; see there
+    for the shapes the kernels serve (above 32 classes: the torch twin) and the zero-tensor difference."""
+    return seg_criteria(logits, target, [dict(type="FocalLoss", gamma=gamma, alpha=alpha)], ignore_index, use_kernels)
+
+
+def dice_loss(logits, target, smooth=1, exponent=2, ignore_index: int = -1, use_kernels=None) -> torch.Tensor:
+    """DiceLoss(smooth, exponent, ignore_index) (misc.py:175-223) as the one-term seg_criteria; see there for the shapes the kernels
+    serve (above 32 classes, or an exponent other than 1 / 2 / 3: the torch twin)."""
+    return seg_criteria(logits, target, [dict(type="DiceLoss", smooth=smooth, exponent=exponent)], ignore_index, use_kernels)
 
 
 class _LovaszSoftmax(Function):

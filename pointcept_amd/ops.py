@@ -1092,6 +1092,75 @@ def cross_entropy_bwd(logits: torch.Tensor, target: torch.Tensor, lse: torch.Ten
     return out
 
 
+CRITERIA_ROWS_MAX_C = 32        # csrc/loss_rows.h LR_CP: the register-row path serves every term
+CRITERIA_CE_MAX_C = 1024        # wider rows: the cross-entropy term alone, element-wise
+CRITERIA_CE, CRITERIA_FOCAL, CRITERIA_DICE = 1, 2, 4
+
+
+class CriteriaSpec:
+    """The terms of one fused criteria call (csrc/criteria.hip), as the kernels take them: `flags` (CRITERIA_* bits) and per term its
+    loss_weight and settings; ce_weight / focal_alpha_vec are fp32 [C] tensors on the logits' device or None."""
+
+    __slots__ = ("flags", "ignore_index", "ce_weight", "ce_eps", "ce_sum", "ce_lw", "focal_alpha", "focal_alpha_vec", "focal_gamma",
+                 "focal_lw", "dice_smooth", "dice_exp", "dice_lw")
+
+    def __init__(self, ignore_index: int = -1):
+        self.flags, self.ignore_index = 0, int(ignore_index)
+        self.ce_weight, self.ce_eps, self.ce_sum, self.ce_lw = None, 0.0, False, 1.0
+        self.focal_alpha, self.focal_alpha_vec, self.focal_gamma, self.focal_lw = 0.5, None, 2.0, 1.0
+        self.dice_smooth, self.dice_exp, self.dice_lw = 1.0, 2, 1.0
+
+
+def _criteria_check(spec: CriteriaSpec, lg: torch.Tensor):
+    c = lg.shape[1]
+    if spec.flags == 0 or c > CRITERIA_CE_MAX_C or (c > CRITERIA_ROWS_MAX_C and spec.flags != CRITERIA_CE):
+        raise PtcoreError(f"criteria kernels: terms {spec.flags} over {c} classes (every term up to {CRITERIA_ROWS_MAX_C}, cross entropy "
+                          f"alone up to {CRITERIA_CE_MAX_C})")
+    for name, vec in (("weight", spec.ce_weight), ("alpha", spec.focal_alpha_vec)):
+        if vec is not None and (vec.dtype != torch.float32 or vec.numel() != c or vec.device != lg.device or not vec.is_contiguous()):
+            raise PtcoreError(f"criteria kernels: {name} must be a contiguous fp32 [{c}] tensor on the logits' device")
+
+
+def criteria_rows_fwd(logits: torch.Tensor, target: torch.Tensor, spec: CriteriaSpec):
+    """-> (out [4] fp32 = total, ce, focal, dice -- each term times its loss_weight --, lsum [N] fp32 = log sum_j exp(x_j - max x),
+    coef [4 + 2C] fp32 for criteria_rows_bwd).  One kernel over the rows, the per-workgroup partial rows summed in double in a fixed order, one finish
+    launch; no host read."""
+    require_cuda(logits, target)
+    if target.dtype != torch.int64:
+        raise PtcoreError("target must be int64")
+    lg, rs = _rows_view(logits)
+    n, c = lg.shape
+    _criteria_check(spec, lg)
+    nb, pw = lib().ptc_criteria_partials(n), lib().ptc_criteria_partial_width(c, spec.flags)
+    lse = torch.empty(n, dtype=torch.float32, device=lg.device)
+    partial = torch.empty((nb, pw), dtype=torch.float32, device=lg.device)
+    check(lib().ptc_criteria_fwd(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), spec.ignore_index, spec.flags,
+                                 ptr(spec.ce_weight), float(spec.ce_eps), ptr(spec.focal_alpha_vec), float(spec.focal_alpha),
+                                 float(spec.focal_gamma), int(spec.dice_exp), ptr(lse), ptr(partial), stream_ptr()), "ptc_criteria_fwd")
+    sums = partial.sum(0, dtype=torch.float64)       # fixed-order reduction of <= N/256 partial rows: deterministic
+    out = torch.empty(4, dtype=torch.float32, device=lg.device)
+    coef = torch.empty(4 + 2 * c, dtype=torch.float32, device=lg.device)
+    check(lib().ptc_criteria_finish(ptr(sums), c, spec.flags, spec.ignore_index, ptr(spec.ce_weight), int(bool(spec.ce_sum)),
+                                    float(spec.ce_lw), float(spec.focal_lw), float(spec.dice_lw), float(spec.dice_smooth),
+                                    int(spec.dice_exp), ptr(out), ptr(coef), stream_ptr()), "ptc_criteria_finish")
+    return out, lse, coef
+
+
+def criteria_rows_bwd(logits: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, coef: torch.Tensor, grad: torch.Tensor,
+                      spec: CriteriaSpec) -> torch.Tensor:
+    """dlogits [N, C] (logits' dtype, dense) = grad * d total / d logits; `grad` device scalar."""
+    require_cuda(logits, target, lse, coef, grad)
+    lg, rs = _rows_view(logits)
+    n, c = lg.shape
+    _criteria_check(spec, lg)
+    out = torch.empty((n, c), dtype=lg.dtype, device=lg.device)
+    check(lib().ptc_criteria_bwd(ptr(lg), rs, ptr(target.contiguous()), ptr(lse), ptr(coef), ptr(grad.reshape(1).float().contiguous()),
+                                 n, c, dtype_code(lg), spec.ignore_index, spec.flags, ptr(spec.ce_weight), float(spec.ce_eps),
+                                 ptr(spec.focal_alpha_vec), float(spec.focal_alpha), float(spec.focal_gamma), int(spec.dice_exp),
+                                 ptr(out), stream_ptr()), "ptc_criteria_bwd")
+    return out
+
+
 LOVASZ_DENSE_MAX_C = 64         # csrc/lovasz.hip LV_MAX_C: the dense [C, N] path
 LOVASZ_MAX_C = 1024             # LW_MAX_C: the row-compacted path
 

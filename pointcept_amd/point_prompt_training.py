@@ -133,7 +133,7 @@ class PointPromptTraining(_LanguageHead):
         assert len(conditions) == len(valid_index)
         assert _backbone_type(backbone) in _BACKBONES + (None,)
         self.backbone = build_backbone(backbone)
-        self.criteria = criteria if callable(criteria) else Criteria(criteria, "PPT-v1m1")
+        self.criteria = criteria if callable(criteria) else Criteria(criteria, "PPT-v1m1", row_terms=False)
         self.conditions = conditions
         self.valid_index = valid_index
         self.embedding_table = nn.Embedding(len(conditions), context_channels)
@@ -168,7 +168,7 @@ class PointPromptTrainingDecoupled(nn.Module):
         assert len(conditions) == len(num_classes)
         assert _backbone_type(backbone) in _BACKBONES + (None,)
         self.backbone = build_backbone(backbone)
-        self.criteria = criteria if callable(criteria) else Criteria(criteria, "PPT-v1m2")
+        self.criteria = criteria if callable(criteria) else Criteria(criteria, "PPT-v1m2", row_terms=False)
         self.conditions = conditions
         self.embedding_table = nn.Embedding(len(conditions), context_channels)
         self.backbone_mode = backbone_mode
@@ -204,7 +204,7 @@ class PointPromptTrainingNeo(_LanguageHead):
             class_names = [list(names) for names in _NEO_CLASS_NAMES]
         assert len(conditions) == len(class_names)
         self.backbone = build_backbone(backbone)
-        self.criteria = criteria if callable(criteria) else Criteria(criteria, "PPT-v1m3")
+        self.criteria = criteria if callable(criteria) else Criteria(criteria, "PPT-v1m3", row_terms=False)
         self.conditions = conditions
         self.freeze_backbone = freeze_backbone
         if self.freeze_backbone:

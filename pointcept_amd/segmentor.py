@@ -6,7 +6,9 @@ Inside Pointcept the reference's own DefaultSegmentorV2 wraps the engine backbon
 criteria (pointcept/models/losses/builder.py:22-31 sums the configured terms): "ce" = CrossEntropyLoss(
 ignore_index=-1) (losses/misc.py), "lovasz" = LovaszLoss(mode="multiclass", ignore_index=-1) (losses/lovasz.py);
 the ScanNet config uses both with weight 1 (scannet/semseg-pt-v3m1-0-base.py:49-52).  Default ("ce",) -- the
-criterion bench.py states.
+criterion bench.py states.  `criteria` may also be the reference's own list of config dicts (type=CrossEntropyLoss | FocalLoss |
+DiceLoss | LovaszLoss with their settings, loss_weight and ignore_index): it is routed through criteria.Criteria, each term with the
+ignore_index of its dict, and `loss_weights` does not apply.
 """
 from __future__ import annotations
 
@@ -14,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as PF
+from .criteria import Criteria
 from . import nn as PNN
 from . import ops
 from ._lib import PtcoreError
@@ -23,6 +26,10 @@ from .structure import Point
 class DefaultSegmentorV2(nn.Module):
     def __init__(self, num_classes, backbone_out_channels, backbone, ignore_index=-1, criteria=("ce",), loss_weights=None):
         super().__init__()
+        self.criteria_list = None
+        if len(criteria) > 0 and all(isinstance(c, dict) for c in criteria):      # the reference's config dicts (build_criteria)
+            self.criteria_list = Criteria(list(criteria), "DefaultSegmentorV2")
+            criteria = ()
         for name in criteria:
             if name not in ("ce", "lovasz"):
                 raise ValueError(f"unknown criterion {name!r}")
@@ -34,6 +41,8 @@ class DefaultSegmentorV2(nn.Module):
         self.num_classes = int(num_classes)
 
     def criteria(self, seg_logits, segment, present=None):   # GPU only, like every op of the engine
+        if self.criteria_list is not None:
+            return self.criteria_list(seg_logits, segment)
         loss = 0
         for name, w in zip(self.criteria_names, self.loss_weights):
             if name == "lovasz" and present is not None:
