@@ -9,7 +9,11 @@
  *     library never allocates or frees device memory and keeps no mutable global state.
  *   - ERRORS: every entry point returns PTC_OK (0) or a negative PTC_E* code; it never
  *     throws across the ABI and never calls exit().  ptc_last_error() returns a
- *     thread-local message for the last failing call on this thread.
+ *     thread-local message for the last failing call on this thread.  The rule a binding
+ *     can apply from the declarations alone: an `int` entry point whose last parameter is
+ *     the ptc_stream_t returns such a status; every other entry point (the *_supported
+ *     predicates, the *_workspace_bytes / size queries, ptc_ptv3_block_abi) takes scalars
+ *     only and returns a value.
  *   - STREAMS: all work is enqueued on the hipStream_t passed as `stream` (the Python
  *     host passes torch.cuda.current_stream().cuda_stream).  No implicit synchronisation,
  *     no use of the legacy default stream (contrast the reference's in-repo ops:

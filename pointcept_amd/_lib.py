@@ -1,4 +1,12 @@
-"""ctypes binding of libptcore.so (the C-ABI declared in include/ptcore.h).
+"""ctypes binding of libptcore.so, derived from include/ptcore.h (the C-ABI's one definition).
+
+The header is read once, at import: its declarations give every entry point's restype / argtypes and whether it
+returns a status, its enums and integer #defines give the constants (PTC_F32 ..., REDUCE_CODES, ORDER_CODES,
+block_enums()).  Nothing of the header is written out a second time here; the parser raises on a declaration it
+does not understand.  `lib()` is the CHECKED handle: a status-returning entry point (an `int` one whose last
+parameter is the stream) raises PtcoreError with ptc_last_error()'s message instead of returning a non-zero
+code, so a call site is `lib().ptc_x(...)`.  `lib(checked=False)` is the RAW handle: the same functions
+returning their status integers (`check(rc, name)` raises for those who want it).
 
 `import torch` happens BEFORE the library is loaded so that libptcore.so's DT_NEEDED
 libamdhip64.so.7 resolves to the HIP runtime bundled with PyTorch-ROCm (one runtime, shared device
@@ -7,255 +15,155 @@ and every op wrapper in this package raises on non-CUDA tensors.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
+import re
+import types
+import zlib
 
 import torch  # noqa: F401  (must precede CDLL: provides the HIP runtime)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libptcore.so")
 PROBE_PATH = os.path.join(HERE, "libptcore_hostprobe.so")
+HEADER_PATH = os.path.normpath(os.path.join(HERE, "..", "include", "ptcore.h"))
 
 c_i64, c_int, c_f32, c_size, c_ptr = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 
-# name -> (restype, argtypes); mirrors include/ptcore.h one to one
-_SIGNATURES = {
-    "ptc_version": (ctypes.c_char_p, []),
-    "ptc_last_error": (ctypes.c_char_p, []),
-    "ptc_serialize_encode": (c_int, [c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr]),
-    "ptc_sort_keys_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_sort_keys": (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_exclusive_scan_workspace_bytes": (c_size, [c_i64]),
-    "ptc_exclusive_scan_i32": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_patch_pad_maps": (c_int, [c_ptr, c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_attn_tables": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_pool_maps_workspace_bytes": (c_size, [c_i64]),
-    "ptc_pool_maps_count": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_pool_maps_fill": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "ptc_pool_child_codes": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "ptc_pool_level_counts": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr]),
-    "ptc_gather_rows": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "ptc_gather_rows_add": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "ptc_segment_csr_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_segment_csr_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "ptc_hash_table_size": (c_i64, [c_i64]),
-    "ptc_hash_table_bytes": (c_size, [c_i64]),
-    "ptc_hash_build": (c_int, [c_ptr, c_i64, c_ptr, c_size, c_ptr]),
-    "ptc_rulebook_subm": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_size, c_ptr, c_ptr]),
-    "ptc_rulebook_down_workspace_bytes": (c_size, [c_i64]),
-    "ptc_rulebook_down_count": (c_int, [c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_rulebook_down_fill": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_spconv_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "ptc_ptv3_block_abi": (c_int, []),
-    "ptc_ptv3_block_mlp_fused": (c_int, [c_int, c_int]),
-    "ptc_ptv3_block_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int]),
-    "ptc_ptv3_block_fwd_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_ptv3_block_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_ptv3_block_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_rulebook_blocks_tab_bytes": (c_size, [c_i64]),
-    "ptc_rulebook_blocks": (c_int, [c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_spconv_fwd_blk": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int, c_int,
-                                   c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_spconv_fwd_blk_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
-    "ptc_spconv_wgrad_blk_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
-    "ptc_spconv_wgrad_blk": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int, c_int,
-                                     c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_linear_supported_ex": (c_int, [c_int, c_int, c_int]),
-    "ptc_linear_joint_supported": (c_int, [c_int, c_int, c_int]),
-    "ptc_linear_norm_joint_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_f32, c_ptr, c_int, c_ptr, c_ptr, c_f32, c_int,
-                                          c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_linear_joint_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_int,
-                                     c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_linear_fwd_ex": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_mlp_supported": (c_int, [c_int, c_int]),
-    "ptc_mlp_fwd": (c_int, [c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_mlp_bwd_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_mlp_bwd": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_spconv_wgrad_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
-    "ptc_spconv_wgrad": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size,
-                                 c_ptr]),
-    "ptc_seg_eval_hist": (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr]),
-    "ptc_rope3d": (c_int, [c_ptr, c_int, c_ptr, c_i64, c_int, c_int, c_f32, c_f32, c_ptr]),
-    "ptc_rope3d_xyz": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_f32, c_ptr]),
-    "ptc_layer_norm_supported": (c_int, [c_int]),
-    "ptc_layer_norm_fwd": (c_int, [c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_f32, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_layer_norm_bwd_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_layer_norm_bwd": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
-                                   c_size, c_ptr]),
-    "ptc_add_norm_fwd": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_f32, c_int, c_ptr, c_ptr, c_f32, c_int,
-                                 c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_add_norm_bwd_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_add_norm_bwd": (c_int, [c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
-                                 c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_attn_varlen_fwd": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_f32, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_attn_varlen_bwd_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_attn_varlen_dropout_fwd": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_f32, c_int, c_f32, ctypes.c_uint64, c_ptr, c_ptr, c_ptr]),
-    "ptc_attn_varlen_dropout_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_f32, c_int, c_f32, ctypes.c_uint64,
-                                            c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_attn_varlen_hd_supported": (c_int, [c_int, c_int]),
-    "ptc_attn_varlen_hd_rope_supported": (c_int, [c_int, c_int]),
-    "ptc_attn_varlen_hd_rope_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_attn_varlen_hd_rope_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_int, c_ptr,
-                                            c_ptr, c_size, c_ptr]),
-    "ptc_weight_layouts": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr]),
-    "ptc_cast_many": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_int, c_ptr]),
-    "ptc_pair_dot_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "ptc_pair_dot_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_int,
-                                 c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_pair_aggregate_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "ptc_pair_aggregate_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr,
-                                       c_ptr, c_ptr]),
-    "ptc_attn_rpe_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_int, c_f32, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_attn_rpe_bwd_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
-    "ptc_attn_rpe_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_int, c_f32, c_int, c_ptr,
-                                 c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_attn_varlen_hd_fwd": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_attn_varlen_hd_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_int, c_ptr,
-                                       c_ptr, c_size, c_ptr]),
-    "ptc_attn_varlen_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_f32, c_int, c_ptr,
-                                    c_ptr, c_size, c_ptr]),
-    "ptc_batch_norm_supported": (c_int, [c_int, c_int]),
-    "ptc_batch_norm_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_batch_norm_act_fwd": (c_int, [c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_f32, c_f32, c_int, c_ptr, c_ptr, c_int, c_ptr, c_int,
-                                       c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_batch_norm_act_bwd": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr,
-                                       c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_batch_norm_add_act_fwd": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_f32, c_f32, c_int, c_ptr, c_ptr, c_int, c_ptr, c_int,
-                                           c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_batch_norm_add_act_bwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr,
-                                           c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_column_sum": (c_int, [c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_coord_max": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr]),
-    "ptc_cross_entropy_partials": (c_i64, [c_i64]),
-    "ptc_cross_entropy_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
-    "ptc_cross_entropy_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_i64, c_ptr]),
-    "ptc_knn_query": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_ball_query": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr]),
-    "ptc_edge_rows_fwd": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_i64, c_int, c_ptr]),
-    "ptc_edge_reduce_fwd": (c_int, [c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_ptr, c_ptr]),
-    "ptc_edge_csr_keys": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "ptc_edge_csr_ptr": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "ptc_edge_scatter_bwd": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int, c_int, c_int, c_i64, c_ptr, c_ptr]),
-    "ptc_pair_dot_weighted": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "ptc_pair_segment_sum": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_aggregation_edge_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
-    "ptc_farthest_point_sampling": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
-    "ptc_voxel_keys": (c_int, [c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_grid_cluster_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_grid_cluster_count": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_cluster_center": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "ptc_cluster_agg_state_bytes": (c_size, [c_i64, c_int]),
-    "ptc_cluster_agg_workspace_bytes": (c_size, [c_i64]),
-    "ptc_cluster_agg_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_ptr, c_size,
-                                    c_ptr]),
-    "ptc_cluster_agg_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_size,
-                                    c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_pg_ball_query_workspace_bytes": (c_size, [c_i64]),
-    "ptc_pg_ball_query_count": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_pg_ball_query_fill": (c_int, [c_ptr, c_i64, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_pg_cluster_workspace_bytes": (c_size, [c_i64]),
-    "ptc_pg_cluster_count": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_pg_cluster_fill": (c_int, [c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_pg_proposal_scores": (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_pg_proposal_masks": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "ptc_pg_bias_loss_workspace_bytes": (c_size, [c_i64]),
-    "ptc_pg_bias_loss_fwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_pg_bias_loss_bwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_msc_match_workspace_bytes": (c_size, [c_i64]),
-    "ptc_msc_match": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_msc_select_workspace_bytes": (c_size, [c_i64]),
-    "ptc_msc_select": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_msc_patch_workspace_bytes": (c_size, [c_i64]),
-    "ptc_msc_patch_rank": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_msc_patch_masks": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "ptc_msc_nce_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_msc_nce_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                c_size, c_ptr]),
-    "ptc_msc_nce_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_i64, c_i64, c_f32, c_ptr, c_ptr, c_ptr, c_ptr,
-                                c_size, c_ptr]),
-    "ptc_msc_csc_nce_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
-    "ptc_msc_csc_nce_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_int, c_f32, c_f32, c_f32, c_int]
-                            + [c_ptr] * 14 + [c_ptr, c_size, c_ptr]),
-    "ptc_msc_csc_nce_bwd": (c_int, [c_ptr] * 11 + [c_i64, c_int, c_int, c_i64, c_i64, c_f32, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr,
-                                                    c_size, c_ptr]),
-    "ptc_cac_supported": (c_int, [c_int, c_int]),
-    "ptc_cac_pool_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
-    "ptc_cac_pool_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size,
-                                 c_ptr]),
-    "ptc_cac_pool_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_cac_cos_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
-    "ptc_cac_cos_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_cac_cos_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_cac_distill_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_cac_distill_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_cac_distill_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_sgi_attn_supported": (c_int, [c_int]),
-    "ptc_sgi_attn_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_sgi_attn_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_f32, c_ptr, c_ptr,
-                                 c_ptr]),
-    "ptc_sgi_attn_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr,
-                                 c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_sgi_pack_mask": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
-    "ptc_sgi_match_cost": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_f32,
-                                   c_ptr, c_ptr]),
-    "ptc_sgi_targets": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr,
-                                c_ptr, c_ptr, c_ptr]),
-    "ptc_lovasz_softmax_workspace_bytes": (c_size, [c_i64, c_int]),
-    "ptc_lovasz_softmax": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_lovasz_present": (c_int, [c_ptr, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_lovasz_softmax_rows_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
-    "ptc_lovasz_softmax_rows": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
-                                        c_ptr, c_size, c_ptr]),
-    "ptc_ppt_head_supported": (c_int, [c_int, c_int, c_int, c_int]),
-    "ptc_ppt_head_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
-    "ptc_ppt_head_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr]),
-    "ptc_ppt_head_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_f32, c_f32, c_ptr,
-                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "ptc_sonata_supported": (c_int, [c_int]),
-    "ptc_sonata_groups": (c_i64, [c_i64, c_int, c_int]),
-    "ptc_sonata_colsum": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_i64, c_int, ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_sonata_rowpass": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_i64, c_int, ctypes.c_double, c_ptr, ctypes.c_double, c_ptr, c_ptr, c_int,
-                                   c_ptr, c_ptr, c_ptr]),
-    "ptc_sonata_distill_fwd": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_int, c_i64, c_int, ctypes.c_double,
-                                       ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "ptc_sonata_distill_bwd": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_int, c_i64, c_ptr, c_i64, c_int, ctypes.c_double, ctypes.c_double,
-                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr]),
-    "ptc_concerto_pool_corr": (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
-    "ptc_concerto_pair_keys": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_i64, c_ptr, c_ptr]),
-    "ptc_concerto_patch_mean_bwd": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr]),
-    "ptc_concerto_align_supported": (c_int, [c_int]),
-    "ptc_concerto_align": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, ctypes.c_double, c_ptr, c_ptr, c_ptr,
-                                   c_ptr]),
-    "ptc_criteria_partials": (c_i64, [c_i64]),
-    "ptc_criteria_partial_width": (c_i64, [c_int, c_int]),
-    "ptc_criteria_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_i64, c_int, c_ptr, ctypes.c_double, c_ptr, ctypes.c_double,
-                                 ctypes.c_double, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_criteria_finish": (c_int, [c_ptr, c_int, c_int, c_i64, c_ptr, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                    ctypes.c_double, c_int, c_ptr, c_ptr, c_ptr]),
-    "ptc_criteria_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_i64, c_int, c_ptr, ctypes.c_double,
-                                 c_ptr, ctypes.c_double, ctypes.c_double, c_int, c_ptr, c_ptr]),
-}
-
-PTC_F32, PTC_F16, PTC_BF16 = 0, 1, 2
-REDUCE_CODES = {"sum": 0, "mean": 1, "max": 2, "min": 3}
-ORDER_CODES = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
-
-_lib = None
-
 
 class PtcoreError(RuntimeError):
-    pass
+    """.code: the PTC_E* status of the failing entry point (None for an error raised on the Python side)"""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
+
+
+# ---- include/ptcore.h -> signatures and constants ------------------------------------------------------------------
+_SCALARS = {"int": c_int, "int64_t": c_i64, "size_t": c_size, "uint64_t": ctypes.c_uint64, "float": c_f32, "double": ctypes.c_double}
+_RETURNS = {"const char*": ctypes.c_char_p, "int64_t": c_i64, "size_t": c_size, "int": c_int}
+_DECL = re.compile(r"(const char\*|int64_t|size_t|int)\s+(ptc_\w+)\s*\(([^()]*)\)")
+
+# signatures: name -> (restype, argtypes, is_status);  enums: tag -> {enumerator: value} (anonymous enums under "");
+# constants: every enumerator and every `#define NAME <int>`
+Header = collections.namedtuple("Header", "signatures enums constants")
+
+
+def _is_stream(param: str) -> bool:
+    return param.replace("const ", "").split()[0] == "ptc_stream_t"
+
+
+def parse_header(text: str) -> Header:
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    constants = {name: int(val, 0) for name, val in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\w+)[ \t]*$", text, flags=re.M)
+                 if re.fullmatch(r"-?(0[xX][0-9a-fA-F]+|\d+)", val)}
+    enums = {}
+    for tag, body in re.findall(r"\benum\s*(\w*)\s*\{([^}]*)\}", text):
+        value = 0
+        for item in filter(None, (x.strip() for x in body.split(","))):
+            name, _, init = (p.strip() for p in item.partition("="))
+            try:
+                value = int(init, 0) if init else value
+            except ValueError:
+                raise PtcoreError(f"include/ptcore.h: enumerator `{item}` is not an integer literal") from None
+            enums.setdefault(tag, {})[name] = constants[name] = value
+            value += 1
+    signatures = {}
+    for stmt in re.split(r"[;{}]", re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)):
+        stmt = " ".join(stmt.split())
+        if not re.search(r"\bptc_\w+\s*\(", stmt):
+            continue
+        m = _DECL.fullmatch(stmt)
+        if m is None or m.group(2) in signatures:
+            raise PtcoreError(f"include/ptcore.h: cannot bind the declaration `{stmt}` (return type const char* / int64_t / size_t / "
+                              "int, one declaration per name)")
+        ret, name, params = m.groups()
+        params = [p.strip() for p in params.split(",") if p.strip() not in ("", "void")]
+        argtypes = []
+        for p in params:
+            words = p.replace("const ", "").split()
+            base = " ".join(words[:-1]) or words[0]
+            if "*" in p or _is_stream(p):
+                argtypes.append(c_ptr)
+            elif base in _SCALARS:
+                argtypes.append(_SCALARS[base])
+            else:   # a by-value struct, `long`, ...: nothing the table maps
+                raise PtcoreError(f"include/ptcore.h: parameter `{p}` of `{stmt}` has a type this binding does not map")
+        # the header's rule (ERRORS): an int entry point whose last parameter is the stream returns a status
+        signatures[name] = (_RETURNS[ret], argtypes, ret == "int" and bool(params) and _is_stream(params[-1]))
+    return Header(signatures, enums, constants)
+
+
+def _read_header():
+    try:
+        raw = open(HEADER_PATH, "rb").read()
+    except OSError as e:
+        raise PtcoreError(f"cannot read {HEADER_PATH} (the C-ABI's definition; this binding is derived from it): {e}") from e
+    return parse_header(raw.decode()), f"{zlib.crc32(raw) & 0xffffffff:08x}"
+
+
+HEADER, HEADER_CRC = _read_header()
+# name -> (restype, argtypes): the computed table under the name of the literal it replaces.  Nothing in this tree reads it; it is
+# what a binder written against that literal reads (tests/emu_backend.py as it was before bind() existed still works on this package)
+_SIGNATURES = {name: (restype, argtypes) for name, (restype, argtypes, _) in HEADER.signatures.items()}
+
+PTC_F32, PTC_F16, PTC_BF16 = (HEADER.enums["ptc_dtype"][k] for k in ("PTC_F32", "PTC_F16", "PTC_BF16"))
+DTYPE_CODES = {torch.float32: PTC_F32, torch.float16: PTC_F16, torch.bfloat16: PTC_BF16}
+REDUCE_CODES = {k[len("PTC_REDUCE_"):].lower(): v for k, v in HEADER.enums["ptc_reduce"].items()}                    # "sum": 0, ...
+ORDER_CODES = {k[len("PTC_ORDER_"):].lower().replace("_", "-"): v for k, v in HEADER.enums["ptc_order"].items()}     # "z-trans": 1, ...
+_BLK_ENUMS = {k[len("PTC_BLK_"):]: v for k, v in HEADER.constants.items() if k.startswith("PTC_BLK_")}
 
 
 def exported_symbols():
-    return sorted(_SIGNATURES)
+    return sorted(HEADER.signatures)
 
 
-def lib():
-    """Load libptcore.so (building it first when hipcc is available and the .so is missing)."""
-    global _lib
-    if _lib is not None:
-        return _lib
+def block_enums():
+    """name -> index of the PTC_BLK_* argument tables of ptc_ptv3_block_fwd / _bwd, and "ABI" -> PTC_BLK_ABI, as include/ptcore.h
+    defines them (the header the library was compiled against -- lib() checks its hash)."""
+    return _BLK_ENUMS
+
+
+def bind(cdll, checked: bool, partial: bool = False):
+    """A view of `cdll` with one ctypes function per declaration of the header.  checked: the status-returning ones raise
+    PtcoreError (message of the same library's ptc_last_error()) instead of returning a non-zero code.  Every view has its own
+    function objects (cdll[name]; attribute access on a CDLL would hand out one cached object, and an errcheck set through one
+    view would act in the other).  partial: leave out what the library does not export (the host emulation) instead of raising."""
+    view = types.SimpleNamespace()
+    last_error = cdll["ptc_last_error"]      # the errchecks' own function object: they depend on no view
+    last_error.restype, last_error.argtypes = HEADER.signatures["ptc_last_error"][:2]
+    for name, (restype, argtypes, is_status) in HEADER.signatures.items():
+        try:
+            fn = cdll[name]
+        except AttributeError:   # the library does not export a declared symbol
+            if partial:
+                continue
+            raise
+        fn.restype, fn.argtypes = restype, argtypes
+        if checked and is_status:
+            fn.errcheck = _raiser(name, last_error)
+        setattr(view, name, fn)
+    return view
+
+
+def _raiser(name, last_error):
+    def errcheck(rc, func, args):
+        if rc:
+            raise PtcoreError(f"{name} failed with code {rc}: {last_error().decode('utf-8', 'replace')}", rc)
+        return rc
+    return errcheck
+
+
+_views = None     # (raw, checked) of libptcore.so once it is loaded
+
+
+def lib(checked: bool = True):
+    """libptcore.so (built first when hipcc is available and the library is missing or stale), bound by bind(): the checked handle
+    by default, the raw one (status integers returned) with checked=False."""
+    global _views
+    if _views is not None:      # the path of every op call
+        return _views[checked]
     # build() is mtime-cached (a no-op when nothing changed) and returns the prebuilt library where there is no
     # hipcc (the GPU box): a stale .so can never meet newer ctypes signatures silently
     from . import build as _build
@@ -263,33 +171,26 @@ def lib():
     variant = os.environ.get("PTC_LIB_VARIANT", "")      # compiler-flag A/B builds, see build.VARIANTS
     LIB_PATH = _build.build(variant=variant)
     try:
-        L = ctypes.CDLL(LIB_PATH)
+        cdll = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # fail loudly: no fallback path exists
         raise PtcoreError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    # ptc_version carries a hash of include/ptcore.h as it was when the library was compiled: compare it with the
-    # header next to this binding (present in the repo; absent in a stripped install -> nothing to compare)
-    ver = L.ptc_version().decode()
-    hdr = os.path.join(HERE, "..", "include", "ptcore.h")
-    if os.path.exists(hdr) and "abi " in ver:
-        import zlib
-
-        want = f"{zlib.crc32(open(hdr, 'rb').read()) & 0xffffffff:08x}"
-        got = ver.split("abi ")[1].split(")")[0].split()[0]
-        if got != want:
-            raise PtcoreError(f"{LIB_PATH} was built against another include/ptcore.h (abi {got}, header {want}): rebuild "
-                              "(python -m pointcept_amd.build --force)")
-    _lib = L
-    return L
+    raw = bind(cdll, checked=False)
+    # ptc_version carries a hash of include/ptcore.h as it was when the library was compiled: compare it with the header this
+    # binding was derived from -- equal hashes mean the signatures above are the library's
+    m = re.search(r"abi (\w+)", raw.ptc_version().decode())
+    got = m.group(1) if m else "none"
+    if got != HEADER_CRC:
+        raise PtcoreError(f"{LIB_PATH} was built against another include/ptcore.h (abi {got}, header {HEADER_CRC}): rebuild "
+                          "(python -m pointcept_amd.build --force)")
+    _views = (raw, bind(cdll, checked=True))      # one assignment: another thread sees neither view or both
+    return _views[checked]
 
 
 def check(rc: int, what: str) -> None:
+    """for callers of the raw handle: raise what the checked handle raises"""
     if rc != 0:
         msg = lib().ptc_last_error().decode("utf-8", "replace")
-        raise PtcoreError(f"{what} failed with code {rc}: {msg}")
+        raise PtcoreError(f"{what} failed with code {rc}: {msg}", rc)
 
 
 def stream_ptr() -> int:
@@ -299,13 +200,10 @@ def stream_ptr() -> int:
 
 
 def dtype_code(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
-        return PTC_F32
-    if t.dtype == torch.float16:
-        return PTC_F16
-    if t.dtype == torch.bfloat16:
-        return PTC_BF16
-    raise PtcoreError(f"unsupported feature dtype {t.dtype}")
+    try:
+        return DTYPE_CODES[t.dtype]
+    except KeyError:
+        raise PtcoreError(f"unsupported feature dtype {t.dtype}") from None
 
 
 def require_cuda(*tensors) -> None:
@@ -320,28 +218,17 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
-_blk_enums = None
-
-
-def block_enums():
-    """name -> index of the PTC_BLK_* argument tables of ptc_ptv3_block_fwd / _bwd, read from include/ptcore.h (one definition: the
-    header the library was compiled against -- lib() has checked its hash)."""
-    global _blk_enums
-    if _blk_enums is None:
-        import re
-
-        txt = open(os.path.join(HERE, "..", "include", "ptcore.h")).read()
-        out = {}
-        for body in re.findall(r"enum\s*\{([^}]*)\}", txt):
-            names = [x.strip() for x in body.replace("\n", " ").split(",") if x.strip()]
-            if names and names[0].startswith("PTC_BLK_"):
-                for i, nm in enumerate(names):
-                    out[nm[len("PTC_BLK_"):]] = i
-        out["ABI"] = int(re.search(r"#define\s+PTC_BLK_ABI\s+(\d+)", txt).group(1))
-        _blk_enums = out
-    return _blk_enums
-
-
+# csrc/host_probe.cpp (C++ with function bodies, not a header: its eight signatures are written out)
+_PROBES = {
+    "probe_serialize_encode": (None, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr]),
+    "probe_patch_pad_maps": (None, [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "probe_padded_len": (c_i64, [c_i64, c_i64]),
+    "probe_num_seq": (c_i64, [c_i64, c_i64]),
+    "probe_vox_pack": (ctypes.c_uint64, [c_int, c_int, c_int, c_int]),
+    "probe_vox_hash": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "probe_voxel_keys": (None, [c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr]),
+    "probe_lovasz_steps": (None, [c_ptr, c_i64, c_ptr]),
+}
 _probe = None
 
 
@@ -354,16 +241,7 @@ def host_probe():
 
             _build.build_host_probe()
         _probe = ctypes.CDLL(PROBE_PATH)
-        _probe.probe_serialize_encode.argtypes = [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr]
-        _probe.probe_serialize_encode.restype = None
-        _probe.probe_patch_pad_maps.argtypes = [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]
-        _probe.probe_patch_pad_maps.restype = None
-        _probe.probe_padded_len.argtypes = [c_i64, c_i64]
-        _probe.probe_padded_len.restype = c_i64
-        _probe.probe_num_seq.argtypes = [c_i64, c_i64]
-        _probe.probe_num_seq.restype = c_i64
-        _probe.probe_vox_pack.argtypes = [c_int, c_int, c_int, c_int]
-        _probe.probe_vox_pack.restype = ctypes.c_uint64
-        _probe.probe_vox_hash.argtypes = [ctypes.c_uint64]
-        _probe.probe_vox_hash.restype = ctypes.c_uint64
+        for name, (restype, argtypes) in _PROBES.items():
+            fn = getattr(_probe, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return _probe

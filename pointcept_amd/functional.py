@@ -1214,8 +1214,7 @@ class _BlockFn(Function):
         nbytes = plan["ws_fwd"]
         # transient (the convolution's fragment-ordered weights at 128 channels and more): NOT saved for the backward
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-        _lib.check(ops.lib().ptc_ptv3_block_fwd(iv, fv, pin, pout, None if ws is None else ws.data_ptr(), nbytes, ops.stream_ptr()),
-                   "ptc_ptv3_block_fwd")
+        ops.lib().ptc_ptv3_block_fwd(iv, fv, pin, pout, None if ws is None else ws.data_ptr(), nbytes, ops.stream_ptr())
         ctx.save_for_backward(x0, xc, rs1, rs2, buf16, buf32, x3, xb3, *keep)
         ctx.meta, ctx.plan = meta, plan
         ctx.present = [p is not None for p in params]
@@ -1298,7 +1297,7 @@ class _BlockFn(Function):
             plan["ws"] = int(ops.lib().ptc_ptv3_block_workspace_bytes(n, npad, c, heads))
         nbytes = plan["ws"]
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.check(ops.lib().ptc_ptv3_block_bwd(iv, fv, pin, psv, pg, ws.data_ptr(), nbytes, ops.stream_ptr()), "ptc_ptv3_block_bwd")
+        ops.lib().ptc_ptv3_block_bwd(iv, fv, pin, psv, pg, ws.data_ptr(), nbytes, ops.stream_ptr())
         dx0 = (gscr if x0.dtype == torch.float32 else sbuf)[plan["gx0"]:plan["gx0"] + n * c].view(n, c)
         dxc = sbuf[plan["gxc"]:plan["gxc"] + n * c].view(n, c)
         grads = []

@@ -12,7 +12,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import PtcoreError, check, dtype_code, lib, ptr, require_cuda, stream_ptr
+from ._lib import PtcoreError, check, dtype_code, lib, ptr, require_cuda, stream_ptr  # noqa: F401  (check: for callers of lib(checked=False))
+
+_DT = _lib.DTYPE_CODES      # torch dtype -> ptc_dtype tag
 
 
 def _ws(nbytes: int, device) -> torch.Tensor:
@@ -35,9 +37,8 @@ def serialize_encode(grid_coord: torch.Tensor, batch: Optional[torch.Tensor], de
     k = len(orders)
     oc = (ctypes.c_int * k)(*[_lib.ORDER_CODES[o] for o in orders])
     out = torch.empty((k, n), dtype=torch.int64, device=gc.device)
-    check(lib().ptc_serialize_encode(ptr(gc), 1 if gc.dtype == torch.int64 else 0, ptr(b), n, int(depth),
-                                     ctypes.cast(oc, ctypes.c_void_p), k, ptr(out), stream_ptr()),
-          "ptc_serialize_encode")
+    lib().ptc_serialize_encode(ptr(gc), 1 if gc.dtype == torch.int64 else 0, ptr(b), n, int(depth),
+                               ctypes.cast(oc, ctypes.c_void_p), k, ptr(out), stream_ptr())
     return out
 
 
@@ -55,8 +56,8 @@ def sort_keys(keys: torch.Tensor, begin_bit: int, end_bit: int, want_inverse: bo
     inverse = torch.empty_like(k2) if want_inverse else None
     nbytes = lib().ptc_sort_keys_workspace_bytes(n, k)
     ws = _ws(nbytes, k2.device)
-    check(lib().ptc_sort_keys(ptr(k2), n, k, int(begin_bit), int(end_bit), ptr(order), ptr(inverse), ptr(ws), nbytes,
-                              stream_ptr()), "ptc_sort_keys")
+    lib().ptc_sort_keys(ptr(k2), n, k, int(begin_bit), int(end_bit), ptr(order), ptr(inverse), ptr(ws), nbytes,
+                        stream_ptr())
     if squeeze:
         return order[0], (inverse[0] if want_inverse else None)
     return order, inverse
@@ -69,7 +70,7 @@ def exclusive_scan_i32(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty(n, dtype=torch.int64, device=x.device)
     nbytes = lib().ptc_exclusive_scan_workspace_bytes(n)
     ws = _ws(nbytes, x.device)
-    check(lib().ptc_exclusive_scan_i32(ptr(x), n, ptr(out), ptr(ws), nbytes, stream_ptr()), "ptc_exclusive_scan_i32")
+    lib().ptc_exclusive_scan_i32(ptr(x), n, ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -99,8 +100,8 @@ def patch_pad_maps(offset: torch.Tensor, offset_host: Sequence[int], patch: int)
     unpad = torch.empty(n, dtype=torch.int64, device=dev)
     cu = torch.empty(n_seq + 1, dtype=torch.int32, device=dev)
     dup = torch.empty(n, dtype=torch.int64, device=dev)
-    check(lib().ptc_patch_pad_maps(ptr(off), off.numel(), int(patch), n, n_pad, n_seq, ptr(pad), ptr(unpad), ptr(cu),
-                                   ptr(dup), stream_ptr()), "ptc_patch_pad_maps")
+    lib().ptc_patch_pad_maps(ptr(off), off.numel(), int(patch), n, n_pad, n_seq, ptr(pad), ptr(unpad), ptr(cu),
+                             ptr(dup), stream_ptr())
     return pad, unpad, cu, dup
 
 
@@ -114,8 +115,8 @@ def attn_tables(order: torch.Tensor, inverse: torch.Tensor, pad: torch.Tensor, u
     t2 = torch.empty((2, n), dtype=torch.int32, device=dev)
     t3 = torch.empty((1, n), dtype=torch.int32, device=dev)
     t4 = torch.empty((1, n_pad), dtype=torch.int32, device=dev)
-    check(lib().ptc_attn_tables(ptr(order.contiguous()), ptr(inverse.contiguous()), ptr(pad), ptr(unpad), ptr(dup), n, n_pad,
-                                ptr(t1), ptr(t2), ptr(t3), ptr(t4), stream_ptr()), "ptc_attn_tables")
+    lib().ptc_attn_tables(ptr(order.contiguous()), ptr(inverse.contiguous()), ptr(pad), ptr(unpad), ptr(dup), n, n_pad,
+                          ptr(t1), ptr(t2), ptr(t3), ptr(t4), stream_ptr())
     return t1, t2, t3, t4
 
 
@@ -130,9 +131,8 @@ def pool_level_counts(code0: torch.Tensor, order0: torch.Tensor, batch_shift: in
 
     counts = torch.empty((len(shifts), n_batch), dtype=torch.int64, device=code0.device)
     arr = (ctypes.c_int * len(shifts))(*[int(v) for v in shifts])
-    check(lib().ptc_pool_level_counts(ptr(code0.contiguous()), ptr(order0.contiguous()), code0.numel(), int(batch_shift), int(n_batch),
-                                      ctypes.cast(arr, ctypes.c_void_p), len(shifts), ptr(counts), stream_ptr()),
-          "ptc_pool_level_counts")
+    lib().ptc_pool_level_counts(ptr(code0.contiguous()), ptr(order0.contiguous()), code0.numel(), int(batch_shift), int(n_batch),
+                                ctypes.cast(arr, ctypes.c_void_p), len(shifts), ptr(counts), stream_ptr())
     return counts
 
 
@@ -149,14 +149,13 @@ def pool_maps(code0: torch.Tensor, order0: torch.Tensor, shift: int, n_cluster: 
     ncl = torch.empty(1, dtype=torch.int64, device=dev)
     nbytes = lib().ptc_pool_maps_workspace_bytes(n)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_pool_maps_count(ptr(code0), ptr(order0), n, int(shift), ptr(cluster), ptr(ncl), ptr(ws), nbytes,
-                                    stream_ptr()), "ptc_pool_maps_count")
+    lib().ptc_pool_maps_count(ptr(code0), ptr(order0), n, int(shift), ptr(cluster), ptr(ncl), ptr(ws), nbytes,
+                              stream_ptr())
     if n_cluster is None:
         n_cluster = int(ncl.item())
     idx_ptr = torch.empty(n_cluster + 1, dtype=torch.int64, device=dev)
     head = torch.empty(n_cluster, dtype=torch.int64, device=dev)
-    check(lib().ptc_pool_maps_fill(ptr(order0), ptr(cluster), n, n_cluster, ptr(idx_ptr), ptr(head), stream_ptr()),
-          "ptc_pool_maps_fill")
+    lib().ptc_pool_maps_fill(ptr(order0), ptr(cluster), n, n_cluster, ptr(idx_ptr), ptr(head), stream_ptr())
     return cluster, idx_ptr, head
 
 
@@ -167,8 +166,7 @@ def pool_child_codes(code: torch.Tensor, head: torch.Tensor, shift: int) -> torc
     k, n = code.shape
     nc = head.numel()
     out = torch.empty((k, nc), dtype=torch.int64, device=code.device)
-    check(lib().ptc_pool_child_codes(ptr(code), n, k, ptr(head), nc, int(shift), ptr(out), stream_ptr()),
-          "ptc_pool_child_codes")
+    lib().ptc_pool_child_codes(ptr(code), n, k, ptr(head), nc, int(shift), ptr(out), stream_ptr())
     return out
 
 
@@ -186,7 +184,7 @@ def voxel_keys(coord: torch.Tensor, grid_size: float):
     grid = torch.empty((n, 3), dtype=torch.int64, device=c.device)
     mn = torch.empty(3, dtype=torch.int64, device=c.device)
     key = torch.empty(n, dtype=torch.int64, device=c.device)
-    check(lib().ptc_voxel_keys(ptr(c), n, float(grid_size), ptr(grid), ptr(mn), ptr(key), stream_ptr()), "ptc_voxel_keys")
+    lib().ptc_voxel_keys(ptr(c), n, float(grid_size), ptr(grid), ptr(mn), ptr(key), stream_ptr())
     return grid, mn, key
 
 
@@ -209,8 +207,8 @@ def knn_query(nsample: int, xyz, offset, new_xyz, new_offset):
     m = q.shape[0]
     idx = torch.empty((m, nsample), dtype=torch.int32, device=x.device)
     dist = torch.empty((m, nsample), dtype=torch.float32, device=x.device)
-    check(lib().ptc_knn_query(ptr(x), ptr(off), ptr(q), ptr(noff), off.numel(), x.shape[0], m, int(nsample), ptr(idx), ptr(dist),
-                              stream_ptr()), "ptc_knn_query")
+    lib().ptc_knn_query(ptr(x), ptr(off), ptr(q), ptr(noff), off.numel(), x.shape[0], m, int(nsample), ptr(idx), ptr(dist),
+                        stream_ptr())
     return idx, dist
 
 
@@ -232,8 +230,8 @@ def ball_query(nsample: int, max_radius: float, min_radius: float, xyz, offset, 
     m = q.shape[0]
     idx = torch.empty((m, nsample), dtype=torch.int32, device=x.device)
     d2 = torch.empty((m, nsample), dtype=torch.float32, device=x.device)
-    check(lib().ptc_ball_query(ptr(x), ptr(off), ptr(q), ptr(noff), ptr(order), off.numel(), x.shape[0], m, int(nsample), float(min_radius),
-                               float(max_radius), ptr(idx), ptr(d2), stream_ptr()), "ptc_ball_query")
+    lib().ptc_ball_query(ptr(x), ptr(off), ptr(q), ptr(noff), ptr(order), off.numel(), x.shape[0], m, int(nsample), float(min_radius),
+                         float(max_radius), ptr(idx), ptr(d2), stream_ptr())
     return idx, torch.sqrt(d2)
 
 
@@ -246,8 +244,7 @@ def farthest_point_sampling(xyz, offset, new_offset):
         raise PtcoreError("offset / new_offset must list the same (non-zero) number of scenes")
     idx = torch.zeros(int(noff[-1].item()), dtype=torch.int32, device=x.device)
     tmp = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-    check(lib().ptc_farthest_point_sampling(ptr(x), ptr(off), ptr(noff), off.numel(), x.shape[0], ptr(tmp), ptr(idx), stream_ptr()),
-          "ptc_farthest_point_sampling")
+    lib().ptc_farthest_point_sampling(ptr(x), ptr(off), ptr(noff), off.numel(), x.shape[0], ptr(tmp), ptr(idx), stream_ptr())
     return idx
 
 
@@ -278,8 +275,8 @@ def edge_rows(mode: int, src, a, idx, out=None, out_col0: int = 0):
         out = torch.empty((m, ns, c), dtype=torch.float32, device=src.device)
     if out.dtype != torch.float32 or not out.is_contiguous() or out.shape[:2] != (m, ns):
         raise PtcoreError("edge_rows: out must be a contiguous fp32 [m, nsample, width] tensor")
-    check(lib().ptc_edge_rows_fwd(int(mode), ptr(src), ptr(a), ptr(idx), m * ns, ns, c, src.shape[0], ptr(out), out.shape[2], int(out_col0),
-                                  stream_ptr()), "ptc_edge_rows_fwd")
+    lib().ptc_edge_rows_fwd(int(mode), ptr(src), ptr(a), ptr(idx), m * ns, ns, c, src.shape[0], ptr(out), out.shape[2], int(out_col0),
+                            stream_ptr())
     return out
 
 
@@ -288,8 +285,8 @@ def edge_reduce(mode: int, src, pos, w, idx, m: int, nsample: int, c: int, w_c: 
     require_cuda(src, pos, w, idx)
     out = torch.empty((m, c), dtype=torch.float32, device=(pos if src is None else src).device)
     n_src = 0 if src is None else src.shape[0]
-    check(lib().ptc_edge_reduce_fwd(int(mode), ptr(src), ptr(pos), int(pos_stride), int(pos_col0), ptr(w), ptr(idx), int(m), int(nsample),
-                                    int(c), int(w_c), n_src, ptr(out), stream_ptr()), "ptc_edge_reduce_fwd")
+    lib().ptc_edge_reduce_fwd(int(mode), ptr(src), ptr(pos), int(pos_stride), int(pos_col0), ptr(w), ptr(idx), int(m), int(nsample),
+                              int(c), int(w_c), n_src, ptr(out), stream_ptr())
     return out
 
 
@@ -307,10 +304,10 @@ class EdgeCSR:
         if self.order is None:
             e = self.idx.numel()
             keys = torch.empty(e, dtype=torch.int64, device=self.idx.device)
-            check(lib().ptc_edge_csr_keys(ptr(self.idx), e, self.n_src, ptr(keys), stream_ptr()), "ptc_edge_csr_keys")
+            lib().ptc_edge_csr_keys(ptr(self.idx), e, self.n_src, ptr(keys), stream_ptr())
             self.order, _ = sort_keys(keys, 0, max(1, int(self.n_src).bit_length()), want_inverse=False) if e else (keys, None)
             self.indptr = torch.empty(self.n_src + 1, dtype=torch.int64, device=self.idx.device)
-            check(lib().ptc_edge_csr_ptr(ptr(keys), ptr(self.order), e, self.n_src, ptr(self.indptr), stream_ptr()), "ptc_edge_csr_ptr")
+            lib().ptc_edge_csr_ptr(ptr(keys), ptr(self.order), e, self.n_src, ptr(self.indptr), stream_ptr())
         return self
 
 
@@ -321,8 +318,8 @@ def edge_scatter_bwd(mode: int, csr: EdgeCSR, g, w, nsample: int, c: int, w_c: i
     csr.build()
     g = _f32_rows(g, "grad").reshape(-1, g.shape[-1])
     out = torch.empty((csr.n_src, c), dtype=torch.float32, device=g.device)
-    check(lib().ptc_edge_scatter_bwd(int(mode), ptr(csr.order), ptr(csr.indptr), ptr(g), g.shape[1], int(g_col0), ptr(w), int(nsample), int(c),
-                                     int(w_c), csr.n_src, ptr(out), stream_ptr()), "ptc_edge_scatter_bwd")
+    lib().ptc_edge_scatter_bwd(int(mode), ptr(csr.order), ptr(csr.indptr), ptr(g), g.shape[1], int(g_col0), ptr(w), int(nsample), int(c),
+                               int(w_c), csr.n_src, ptr(out), stream_ptr())
     return out
 
 
@@ -340,8 +337,8 @@ def pair_dot_weighted(a, b, w, ia, ib) -> torch.Tensor:
     if w is not None and w.numel() != c:
         raise PtcoreError(f"pair_dot_weighted: weight has {w.numel()} entries, rows have {c} channels")
     out = torch.empty((ia.numel(), g), dtype=torch.float32, device=a.device)
-    check(lib().ptc_pair_dot_weighted(ptr(a), ptr(b), ptr(w), ptr(ia), ptr(ib), ia.numel(), a.shape[0], b.shape[0], g, c, ptr(out),
-                                      stream_ptr()), "ptc_pair_dot_weighted")
+    lib().ptc_pair_dot_weighted(ptr(a), ptr(b), ptr(w), ptr(ia), ptr(ib), ia.numel(), a.shape[0], b.shape[0], g, c, ptr(out),
+                                stream_ptr())
     return out
 
 
@@ -363,8 +360,8 @@ def pair_segment_sum(s, b, w, self_rows, csr: "EdgeCSR", oidx, want_prod: bool =
         if tuple(self_rows.shape) != (csr.n_src, g, c):
             raise PtcoreError("pair_segment_sum: self rows do not match the output")
         prod = torch.empty_like(out)
-    check(lib().ptc_pair_segment_sum(ptr(s), ptr(b), ptr(w), ptr(self_rows) if want_prod else None, ptr(csr.order), ptr(csr.indptr), ptr(oidx),
-                                     csr.n_src, b.shape[0], g, c, ptr(out), ptr(prod), stream_ptr()), "ptc_pair_segment_sum")
+    lib().ptc_pair_segment_sum(ptr(s), ptr(b), ptr(w), ptr(self_rows) if want_prod else None, ptr(csr.order), ptr(csr.indptr), ptr(oidx),
+                               csr.n_src, b.shape[0], g, c, ptr(out), ptr(prod), stream_ptr())
     return out, prod
 
 
@@ -373,8 +370,8 @@ def aggregation_edge_bwd(src, pos, w, idx, g):
     require_cuda(src, pos, w, idx, g)
     m, ns, c = pos.shape
     gp, gw = torch.empty_like(pos), torch.empty_like(w)
-    check(lib().ptc_aggregation_edge_bwd(ptr(src), ptr(pos), ptr(w), ptr(idx), ptr(g), m, ns, c, w.shape[-1], src.shape[0], ptr(gp), ptr(gw),
-                                         stream_ptr()), "ptc_aggregation_edge_bwd")
+    lib().ptc_aggregation_edge_bwd(ptr(src), ptr(pos), ptr(w), ptr(idx), ptr(g), m, ns, c, w.shape[-1], src.shape[0], ptr(gp), ptr(gw),
+                                   stream_ptr())
     return gp, gw
 
 
@@ -392,8 +389,8 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor, idx2: Optional[torch.Tenso
         idx2 = idx2.to(torch.int64).contiguous()
     n_out, c = idx.numel(), src.shape[1]
     out = torch.empty((n_out, c), dtype=src.dtype, device=src.device)
-    check(lib().ptc_gather_rows(ptr(src), src.shape[0], ptr(idx), ptr(idx2), n_out, c, dtype_code(src), ptr(out),
-                                stream_ptr()), "ptc_gather_rows")
+    lib().ptc_gather_rows(ptr(src), src.shape[0], ptr(idx), ptr(idx2), n_out, c, dtype_code(src), ptr(out),
+                          stream_ptr())
     return out
 
 
@@ -410,8 +407,7 @@ def gather_rows_add(src: torch.Tensor, idx: torch.Tensor, addend: torch.Tensor) 
     src, addend = src.contiguous(), addend.contiguous()
     idx = idx.to(torch.int64).contiguous()
     out = torch.empty_like(addend)
-    check(lib().ptc_gather_rows_add(ptr(src), src.shape[0], ptr(idx), ptr(addend), idx.numel(), src.shape[1], dtype_code(src), ptr(out), stream_ptr()),
-          "ptc_gather_rows_add")
+    lib().ptc_gather_rows_add(ptr(src), src.shape[0], ptr(idx), ptr(addend), idx.numel(), src.shape[1], dtype_code(src), ptr(out), stream_ptr())
     return out
 
 
@@ -425,8 +421,8 @@ def segment_csr_fwd(src: torch.Tensor, perm: Optional[torch.Tensor], indptr: tor
     n_seg, c = indptr.numel() - 1, src.shape[1]
     out = torch.empty((n_seg, c), dtype=src.dtype, device=src.device)
     arg = torch.empty((n_seg, c), dtype=torch.int32, device=src.device) if reduce in ("max", "min") else None
-    check(lib().ptc_segment_csr_fwd(ptr(src), ptr(perm), ptr(indptr), n_seg, c, dtype_code(src),
-                                    _lib.REDUCE_CODES[reduce], ptr(out), ptr(arg), stream_ptr()), "ptc_segment_csr_fwd")
+    lib().ptc_segment_csr_fwd(ptr(src), ptr(perm), ptr(indptr), n_seg, c, dtype_code(src),
+                              _lib.REDUCE_CODES[reduce], ptr(out), ptr(arg), stream_ptr())
     return out, arg
 
 
@@ -439,9 +435,8 @@ def segment_csr_bwd(grad_out: torch.Tensor, perm: Optional[torch.Tensor], indptr
     covered = int(n_src)
     alloc = torch.empty if covers_all else torch.zeros      # covers_all: every row belongs to a segment and gets written
     gsrc = alloc((covered, c), dtype=grad_out.dtype, device=grad_out.device)
-    check(lib().ptc_segment_csr_bwd(ptr(grad_out), ptr(perm), ptr(indptr), ptr(arg), n_seg, covered, c,
-                                    dtype_code(grad_out), _lib.REDUCE_CODES[reduce], ptr(gsrc), stream_ptr()),
-          "ptc_segment_csr_bwd")
+    lib().ptc_segment_csr_bwd(ptr(grad_out), ptr(perm), ptr(indptr), ptr(arg), n_seg, covered, c,
+                              dtype_code(grad_out), _lib.REDUCE_CODES[reduce], ptr(gsrc), stream_ptr())
     return gsrc
 
 
@@ -478,7 +473,7 @@ class HashTable:
         self.size = int(lib().ptc_hash_table_size(n))            # buckets of 2x2x2 voxels, 64 bytes each
         self.nbytes = int(lib().ptc_hash_table_bytes(n))
         self.buf = torch.empty(self.nbytes // 8, dtype=torch.int64, device=indices.device)   # torch allocations are >= 256 B aligned
-        check(lib().ptc_hash_build(ptr(self.indices), n, ptr(self.buf), self.nbytes, stream_ptr()), "ptc_hash_build")
+        lib().ptc_hash_build(ptr(self.indices), n, ptr(self.buf), self.nbytes, stream_ptr())
 
 
 def rulebook_subm(indices: torch.Tensor, ksize: int, table: Optional[HashTable] = None) -> torch.Tensor:
@@ -488,8 +483,7 @@ def rulebook_subm(indices: torch.Tensor, ksize: int, table: Optional[HashTable] 
     ind = table.indices
     n = ind.shape[0]
     nbr = torch.empty((ksize ** 3, n), dtype=torch.int32, device=ind.device)
-    check(lib().ptc_rulebook_subm(ptr(ind), n, int(ksize), ptr(table.buf), table.nbytes, ptr(nbr), stream_ptr()),
-          "ptc_rulebook_subm")
+    lib().ptc_rulebook_subm(ptr(ind), n, int(ksize), ptr(table.buf), table.nbytes, ptr(nbr), stream_ptr())
     return nbr
 
 
@@ -515,8 +509,8 @@ class BlockTables:
         self.hid = torch.empty((nblk, self.hcap), dtype=torch.int32, device=dev)
         self.hcnt = torch.empty(nblk, dtype=torch.int32, device=dev)
         self.n_overflow = torch.empty(1, dtype=torch.int32, device=dev)
-        check(lib().ptc_rulebook_blocks(ptr(self.nbr), kv, n, self.bm, self.hcap, ptr(self.tab), ptr(self.hid), ptr(self.hcnt),
-                                        ptr(self.n_overflow), stream_ptr()), "ptc_rulebook_blocks")
+        lib().ptc_rulebook_blocks(ptr(self.nbr), kv, n, self.bm, self.hcap, ptr(self.tab), ptr(self.hid), ptr(self.hcnt),
+                                  ptr(self.n_overflow), stream_ptr())
 
 
 def block_plan(c_in: int, c_out: int, kv: int, dtype: torch.dtype, n_rows: int = 1 << 30):
@@ -568,14 +562,14 @@ def rulebook_down(indices: torch.Tensor, coord_bits: int, batch_bits: int):
     n_out_dev = torch.empty(1, dtype=torch.int64, device=dev)
     nbytes = lib().ptc_rulebook_down_workspace_bytes(n)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_rulebook_down_count(ptr(ind), n, int(coord_bits), int(batch_bits), ptr(out_of_in), ptr(n_out_dev),
-                                        ptr(ws), nbytes, stream_ptr()), "ptc_rulebook_down_count")
+    lib().ptc_rulebook_down_count(ptr(ind), n, int(coord_bits), int(batch_bits), ptr(out_of_in), ptr(n_out_dev),
+                                  ptr(ws), nbytes, stream_ptr())
     n_out = int(n_out_dev.item())
     out_indices = torch.empty((n_out, 4), dtype=torch.int32, device=dev)
     nbr_down = torch.empty((8, n_out), dtype=torch.int32, device=dev)
     nbr_up = torch.empty((8, n), dtype=torch.int32, device=dev)
-    check(lib().ptc_rulebook_down_fill(ptr(ind), n, ptr(out_of_in), n_out, ptr(out_indices), ptr(nbr_down), ptr(nbr_up),
-                                       stream_ptr()), "ptc_rulebook_down_fill")
+    lib().ptc_rulebook_down_fill(ptr(ind), n, ptr(out_of_in), n_out, ptr(out_indices), ptr(nbr_down), ptr(nbr_up),
+                                 stream_ptr())
     return out_indices, nbr_down, nbr_up
 
 
@@ -616,12 +610,12 @@ def spconv_fwd(feat: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
         if nbytes is None:
             nbytes = _fwd_blk_ws[(kv, c_in, c_out)] = int(lib().ptc_spconv_fwd_blk_workspace_bytes(n_out, kv, c_in, c_out))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device) if nbytes else None
-        check(lib().ptc_spconv_fwd_blk(ptr(feat), feat.shape[0], ptr(weight), ptr(bias), ptr(nbr), ptr(blk.tab), ptr(blk.hid),
-                                       ptr(blk.hcnt), blk.bm, blk.hcap, n_out, kv, c_in, c_out, dtype_code(feat), ptr(out),
-                                       ptr(ws), nbytes, stream_ptr()), "ptc_spconv_fwd_blk")
+        lib().ptc_spconv_fwd_blk(ptr(feat), feat.shape[0], ptr(weight), ptr(bias), ptr(nbr), ptr(blk.tab), ptr(blk.hid),
+                                 ptr(blk.hcnt), blk.bm, blk.hcap, n_out, kv, c_in, c_out, dtype_code(feat), ptr(out),
+                                 ptr(ws), nbytes, stream_ptr())
         return out
-    check(lib().ptc_spconv_fwd(ptr(feat), feat.shape[0], ptr(weight), ptr(bias), ptr(nbr), n_out, kv, c_in, c_out,
-                               dtype_code(feat), ptr(out), stream_ptr()), "ptc_spconv_fwd")
+    lib().ptc_spconv_fwd(ptr(feat), feat.shape[0], ptr(weight), ptr(bias), ptr(nbr), n_out, kv, c_in, c_out,
+                         dtype_code(feat), ptr(out), stream_ptr())
     return out
 
 
@@ -648,15 +642,15 @@ def spconv_wgrad(feat: torch.Tensor, dout: torch.Tensor, nbr: Optional[torch.Ten
             raise PtcoreError("blk was built from another gather table")
         nbytes = lib().ptc_spconv_wgrad_blk_workspace_bytes(n_out, kv, c_in, c_out)
         ws = _ws(nbytes, feat.device)
-        check(lib().ptc_spconv_wgrad_blk(ptr(feat), feat.shape[0], ptr(dout), ptr(nbr), ptr(blk.tab), ptr(blk.hid), ptr(blk.hcnt),
-                                         ptr(blk.n_overflow), blk.bm, blk.hcap, n_out, kv, c_in, c_out, dtype_code(feat), ptr(dw), ptr(ws),
-                                         nbytes, stream_ptr()), "ptc_spconv_wgrad_blk")
+        lib().ptc_spconv_wgrad_blk(ptr(feat), feat.shape[0], ptr(dout), ptr(nbr), ptr(blk.tab), ptr(blk.hid), ptr(blk.hcnt),
+                                   ptr(blk.n_overflow), blk.bm, blk.hcap, n_out, kv, c_in, c_out, dtype_code(feat), ptr(dw), ptr(ws),
+                                   nbytes, stream_ptr())
         return dw
     db = torch.empty(c_out, dtype=torch.float32, device=feat.device) if want_bias else None
     nbytes = lib().ptc_spconv_wgrad_workspace_bytes(n_out, kv, c_in, c_out)
     ws = _ws(nbytes, feat.device)
-    check(lib().ptc_spconv_wgrad(ptr(feat), feat.shape[0], ptr(dout), ptr(nbr), n_out, kv, c_in, c_out,
-                                 dtype_code(feat), ptr(dw), ptr(db), ptr(ws), nbytes, stream_ptr()), "ptc_spconv_wgrad")
+    lib().ptc_spconv_wgrad(ptr(feat), feat.shape[0], ptr(dout), ptr(nbr), n_out, kv, c_in, c_out,
+                           dtype_code(feat), ptr(dw), ptr(db), ptr(ws), nbytes, stream_ptr())
     return (dw, db) if want_bias else dw
 
 
@@ -677,8 +671,7 @@ def seg_eval_hist(logits: Optional[torch.Tensor], target: torch.Tensor, k: int, 
         pred = pred.reshape(-1).to(torch.int64).contiguous()
         if pred.numel() != m:
             raise PtcoreError("pred / target size mismatch")            # misc.py:60
-        check(lib().ptc_seg_eval_hist(0, 0, 0, 0, ptr(pred), 0, ptr(target), m, 0, int(k), int(ignore_index), ptr(hist), stream_ptr()),
-              "ptc_seg_eval_hist")
+        lib().ptc_seg_eval_hist(0, 0, 0, 0, ptr(pred), 0, ptr(target), m, 0, int(k), int(ignore_index), ptr(hist), stream_ptr())
     else:
         if logits.dim() != 2 or logits.stride(1) != 1:
             raise PtcoreError("logits must be [N, C] with unit column stride")
@@ -688,8 +681,8 @@ def seg_eval_hist(logits: Optional[torch.Tensor], target: torch.Tensor, k: int, 
                 raise PtcoreError("inverse / target size mismatch")
         elif logits.shape[0] != m:
             raise PtcoreError("logits / target size mismatch")
-        check(lib().ptc_seg_eval_hist(ptr(logits), dtype_code(logits), logits.stride(0), logits.shape[1], 0, ptr(inverse), ptr(target), m,
-                                      logits.shape[0], int(k), int(ignore_index), ptr(hist), stream_ptr()), "ptc_seg_eval_hist")
+        lib().ptc_seg_eval_hist(ptr(logits), dtype_code(logits), logits.stride(0), logits.shape[1], 0, ptr(inverse), ptr(target), m,
+                                logits.shape[0], int(k), int(ignore_index), ptr(hist), stream_ptr())
     return hist[0], hist[1] + hist[2] - hist[0], hist[2]
 
 
@@ -707,7 +700,7 @@ def rope3d_(tokens: torch.Tensor, positions: torch.Tensor, base: float, fwd: flo
     n = tokens.numel() // (H * D) if H * D > 0 else 0
     if positions.numel() != 3 * n:
         raise PtcoreError(f"positions {tuple(positions.shape)} do not match tokens {tuple(tokens.shape)}")
-    check(lib().ptc_rope3d(ptr(tokens), dtype_code(tokens), ptr(positions), n, H, D, float(base), float(fwd), stream_ptr()), "ptc_rope3d")
+    lib().ptc_rope3d(ptr(tokens), dtype_code(tokens), ptr(positions), n, H, D, float(base), float(fwd), stream_ptr())
     return tokens
 
 
@@ -727,17 +720,14 @@ def rope3d_xyz(qkv: torch.Tensor, xyz: torch.Tensor, inv_freq: torch.Tensor, rot
     if inv_freq.dtype != torch.float32 or inv_freq.numel() != D // 6 or not inv_freq.is_contiguous():
         raise PtcoreError(f"rope3d_xyz: inv_freq must be contiguous fp32 [{D // 6}]")
     out = torch.empty(qkv.shape, dtype=out_dtype or qkv.dtype, device=qkv.device)
-    check(lib().ptc_rope3d_xyz(ptr(qkv), dtype_code(qkv), ptr(out), dtype_code(out), ptr(xyz), ptr(inv_freq), n, S, int(rot_slabs), H, D,
-                               float(sign), stream_ptr()), "ptc_rope3d_xyz")
+    lib().ptc_rope3d_xyz(ptr(qkv), dtype_code(qkv), ptr(out), dtype_code(out), ptr(xyz), ptr(inv_freq), n, S, int(rot_slabs), H, D,
+                         float(sign), stream_ptr())
     return out
 
 
 # ------------------------------------------------------------------------------------------------
 # layer norm
 # ------------------------------------------------------------------------------------------------
-_DT = {torch.float32: _lib.PTC_F32, torch.float16: _lib.PTC_F16, torch.bfloat16: _lib.PTC_BF16}
-
-
 def layer_norm_supported(c: int) -> bool:
     """the power-of-two instances (C = 32 .. 512): the widths the GEMM-epilogue joints and the Block executor are built for"""
     return lib().ptc_layer_norm_supported(int(c)) == 1
@@ -763,8 +753,8 @@ def layer_norm_fwd(x: torch.Tensor, gamma, beta, eps: float, out_dtype: torch.dt
     y = torch.empty((n, c), dtype=out_dtype, device=x.device)
     mean = torch.empty(n, dtype=torch.float32, device=x.device)
     rstd = torch.empty(n, dtype=torch.float32, device=x.device)
-    check(lib().ptc_layer_norm_fwd(ptr(x), n, c, dtype_code(x), ptr(g), ptr(b), float(eps), ptr(y), _DT[out_dtype],
-                                   ptr(mean), ptr(rstd), stream_ptr()), "ptc_layer_norm_fwd")
+    lib().ptc_layer_norm_fwd(ptr(x), n, c, dtype_code(x), ptr(g), ptr(b), float(eps), ptr(y), _DT[out_dtype],
+                             ptr(mean), ptr(rstd), stream_ptr())
     return y, mean, rstd
 
 
@@ -780,8 +770,8 @@ def layer_norm_bwd(dy: torch.Tensor, x: torch.Tensor, mean, rstd, gamma, want_af
     db = torch.empty(c, dtype=torch.float32, device=x.device) if want_affine else None
     nbytes = lib().ptc_layer_norm_bwd_workspace_bytes(n, c)
     ws = _ws(nbytes, x.device)
-    check(lib().ptc_layer_norm_bwd(ptr(dy), dtype_code(dy), ptr(x), dtype_code(x), ptr(mean), ptr(rstd), ptr(g), n, c,
-                                   ptr(dx), ptr(dg), ptr(db), ptr(ws), nbytes, stream_ptr()), "ptc_layer_norm_bwd")
+    lib().ptc_layer_norm_bwd(ptr(dy), dtype_code(dy), ptr(x), dtype_code(x), ptr(mean), ptr(rstd), ptr(g), n, c,
+                             ptr(dx), ptr(dg), ptr(db), ptr(ws), nbytes, stream_ptr())
     return dx, dg, db
 
 
@@ -802,10 +792,9 @@ def add_norm_fwd(u, a, row_scale, norm_a, norm_b, y_dtype):
     ga, ba, ea = norm_a if norm_a is not None else (None, None, 0.0)
     gb, bb, eb = norm_b if norm_b is not None else (None, None, 0.0)
     rs = None if row_scale is None else row_scale.to(torch.float32).contiguous()
-    check(lib().ptc_add_norm_fwd(ptr(u), dtype_code(u), ptr(a), dtype_code(a), ptr(rs), n, c, ptr(ga), ptr(ba), float(ea),
-                                 int(norm_a is not None), ptr(gb), ptr(bb), float(eb), int(norm_b is not None), ptr(z), ptr(y),
-                                 _DT[y_dtype] if y_dtype is not None else 0, ptr(st_a), ptr(st_b), stream_ptr()),
-          "ptc_add_norm_fwd")
+    lib().ptc_add_norm_fwd(ptr(u), dtype_code(u), ptr(a), dtype_code(a), ptr(rs), n, c, ptr(ga), ptr(ba), float(ea),
+                           int(norm_a is not None), ptr(gb), ptr(bb), float(eb), int(norm_b is not None), ptr(z), ptr(y),
+                           _DT[y_dtype] if y_dtype is not None else 0, ptr(st_a), ptr(st_b), stream_ptr())
     return z, y, st_a, st_b
 
 
@@ -832,8 +821,8 @@ def linear_joint_fwd(x, weight, bias, table, a, row_scale, norm_b, y_dtype, n_ou
     gb, bb, eb = norm_b if norm_b is not None else (None, None, 0.0)
     rs = None if row_scale is None else row_scale.to(torch.float32).contiguous()
     b = None if bias is None else bias.float().contiguous()
-    check(lib().ptc_linear_joint_fwd(ptr(x), x.shape[0], ptr(weight), ptr(b), ptr(tab), n, c_in, c_out, dtype_code(x), ptr(a), ptr(rs), ptr(gb), ptr(bb),
-                                     float(eb), int(norm_b is not None), ptr(z), ptr(y), ptr(st_b), stream_ptr()), "ptc_linear_joint_fwd")
+    lib().ptc_linear_joint_fwd(ptr(x), x.shape[0], ptr(weight), ptr(b), ptr(tab), n, c_in, c_out, dtype_code(x), ptr(a), ptr(rs), ptr(gb), ptr(bb),
+                               float(eb), int(norm_b is not None), ptr(z), ptr(y), ptr(st_b), stream_ptr())
     return z, y, st_b
 
 
@@ -855,9 +844,9 @@ def linear_norm_joint_fwd(x, weight, bias, norm_a, a, norm_b, y_dtype):
     ga, ba, ea = norm_a
     gb, bb, eb = norm_b if norm_b is not None else (None, None, 0.0)
     b = None if bias is None else bias.float().contiguous()
-    check(lib().ptc_linear_norm_joint_fwd(ptr(x), x.shape[0], ptr(weight), ptr(b), n, c_in, c_out, dtype_code(x), ptr(ga), ptr(ba), float(ea), ptr(a),
-                                          dtype_code(a), ptr(gb), ptr(bb), float(eb), int(norm_b is not None), ptr(u), ptr(z), ptr(y), ptr(st_a), ptr(st_b),
-                                          stream_ptr()), "ptc_linear_norm_joint_fwd")
+    lib().ptc_linear_norm_joint_fwd(ptr(x), x.shape[0], ptr(weight), ptr(b), n, c_in, c_out, dtype_code(x), ptr(ga), ptr(ba), float(ea), ptr(a),
+                                    dtype_code(a), ptr(gb), ptr(bb), float(eb), int(norm_b is not None), ptr(u), ptr(z), ptr(y), ptr(st_a), ptr(st_b),
+                                    stream_ptr())
     return u, z, y, st_a, st_b
 
 
@@ -875,10 +864,10 @@ def add_norm_bwd(dz_in, dy, z, u, row_scale, g_a, st_a, g_b, st_b, want_affine_a
     dga, dba, dgb, dbb = mk(want_affine_a), mk(want_affine_a), mk(want_affine_b), mk(want_affine_b)
     nbytes = lib().ptc_add_norm_bwd_workspace_bytes(n, c)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_add_norm_bwd(ptr(dz_in), ptr(dy), dtype_code(dy) if dy is not None else 0, ptr(z), ptr(u), dtype_code(u),
-                                 ptr(row_scale), n, c, ptr(g_a), ptr(st_a), int(st_a is not None), ptr(g_b), ptr(st_b),
-                                 int(st_b is not None), ptr(da), dtype_code(da), ptr(du), ptr(dga), ptr(dba), ptr(dgb), ptr(dbb), ptr(ws),
-                                 nbytes, stream_ptr()), "ptc_add_norm_bwd")
+    lib().ptc_add_norm_bwd(ptr(dz_in), ptr(dy), dtype_code(dy) if dy is not None else 0, ptr(z), ptr(u), dtype_code(u),
+                           ptr(row_scale), n, c, ptr(g_a), ptr(st_a), int(st_a is not None), ptr(g_b), ptr(st_b),
+                           int(st_b is not None), ptr(da), dtype_code(da), ptr(du), ptr(dga), ptr(dba), ptr(dgb), ptr(dbb), ptr(ws),
+                           nbytes, stream_ptr())
     return da, du, dga, dba, dgb, dbb
 
 
@@ -909,14 +898,14 @@ def attn_varlen_fwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int
     if dropout_p > 0.0:       # attention dropout (csrc/attention_drop.h): head_dim 16; the mask is a function of `seed`, regenerated by the backward
         if D != 16:
             raise PtcoreError("attention dropout is implemented for head_dim 16")
-        check(lib().ptc_attn_varlen_dropout_fwd(ptr(qkv), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen), float(softmax_scale), dtype_code(qkv),
-                                                float(dropout_p), int(seed), ptr(out), ptr(lse), stream_ptr()), "ptc_attn_varlen_dropout_fwd")
+        lib().ptc_attn_varlen_dropout_fwd(ptr(qkv), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen), float(softmax_scale), dtype_code(qkv),
+                                          float(dropout_p), int(seed), ptr(out), ptr(lse), stream_ptr())
     elif D == 16:
-        check(lib().ptc_attn_varlen_fwd(ptr(qkv), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen), float(softmax_scale),
-                                        dtype_code(qkv), ptr(out), ptr(lse), stream_ptr()), "ptc_attn_varlen_fwd")
+        lib().ptc_attn_varlen_fwd(ptr(qkv), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen), float(softmax_scale),
+                                  dtype_code(qkv), ptr(out), ptr(lse), stream_ptr())
     else:
-        check(lib().ptc_attn_varlen_hd_fwd(ptr(qkv), ptr(cu), cu.numel() - 1, T, H, D, int(max_seqlen), float(softmax_scale),
-                                           dtype_code(qkv), ptr(out), ptr(lse), stream_ptr()), "ptc_attn_varlen_hd_fwd")
+        lib().ptc_attn_varlen_hd_fwd(ptr(qkv), ptr(cu), cu.numel() - 1, T, H, D, int(max_seqlen), float(softmax_scale),
+                                     dtype_code(qkv), ptr(out), ptr(lse), stream_ptr())
     return out, lse
 
 
@@ -931,17 +920,17 @@ def attn_varlen_bwd(qkv, out, dout, lse, cu_seqlens, max_seqlen: int, softmax_sc
     nbytes = lib().ptc_attn_varlen_bwd_workspace_bytes(T, H)
     ws = _ws(nbytes, qkv.device)
     if dropout_p > 0.0:
-        check(lib().ptc_attn_varlen_dropout_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen),
-                                                float(softmax_scale), dtype_code(qkv), float(dropout_p), int(seed), ptr(dqkv), ptr(ws), nbytes,
-                                                stream_ptr()), "ptc_attn_varlen_dropout_bwd")
+        lib().ptc_attn_varlen_dropout_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen),
+                                          float(softmax_scale), dtype_code(qkv), float(dropout_p), int(seed), ptr(dqkv), ptr(ws), nbytes,
+                                          stream_ptr())
     elif D == 16:
-        check(lib().ptc_attn_varlen_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), cu.numel() - 1, T, H,
-                                        int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(ws), nbytes,
-                                        stream_ptr()), "ptc_attn_varlen_bwd")
+        lib().ptc_attn_varlen_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), cu.numel() - 1, T, H,
+                                  int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(ws), nbytes,
+                                  stream_ptr())
     else:
-        check(lib().ptc_attn_varlen_hd_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), cu.numel() - 1, T, H, D,
-                                           int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(ws), nbytes,
-                                           stream_ptr()), "ptc_attn_varlen_hd_bwd")
+        lib().ptc_attn_varlen_hd_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), cu.numel() - 1, T, H, D,
+                                     int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(ws), nbytes,
+                                     stream_ptr())
     return dqkv
 
 
@@ -963,8 +952,8 @@ def attn_rope_fwd(qkv, xyz, inv_freq, cu_seqlens, max_seqlen: int, softmax_scale
     cu = cu_seqlens.to(torch.int32).contiguous()
     out = torch.empty((T, H, D), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((H, T), dtype=torch.float32, device=qkv.device)
-    check(lib().ptc_attn_varlen_hd_rope_fwd(ptr(qkv), ptr(cu), ptr(xyz), ptr(inv_freq), cu.numel() - 1, T, H, D, int(max_seqlen),
-                                            float(softmax_scale), dtype_code(qkv), ptr(out), ptr(lse), stream_ptr()), "ptc_attn_varlen_hd_rope_fwd")
+    lib().ptc_attn_varlen_hd_rope_fwd(ptr(qkv), ptr(cu), ptr(xyz), ptr(inv_freq), cu.numel() - 1, T, H, D, int(max_seqlen),
+                                      float(softmax_scale), dtype_code(qkv), ptr(out), ptr(lse), stream_ptr())
     return out, lse
 
 
@@ -979,9 +968,8 @@ def attn_rope_bwd(qkv, out, dout, lse, xyz, inv_freq, cu_seqlens, max_seqlen: in
     dqkv = torch.empty_like(qkv)
     nbytes = lib().ptc_attn_varlen_bwd_workspace_bytes(T, H)
     ws = _ws(nbytes, qkv.device)
-    check(lib().ptc_attn_varlen_hd_rope_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), ptr(xyz), ptr(inv_freq), cu.numel() - 1, T, H, D,
-                                            int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(ws), nbytes, stream_ptr()),
-          "ptc_attn_varlen_hd_rope_bwd")
+    lib().ptc_attn_varlen_hd_rope_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), ptr(xyz), ptr(inv_freq), cu.numel() - 1, T, H, D,
+                                      int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(ws), nbytes, stream_ptr())
     return dqkv
 
 
@@ -1016,8 +1004,8 @@ def attn_rpe_fwd(qkv, cu_seqlens, max_seqlen: int, softmax_scale: float, grid_co
     cu = cu_seqlens.to(torch.int32).contiguous()
     out = torch.empty((T, H, 16), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((H, T), dtype=torch.float32, device=qkv.device)
-    check(lib().ptc_attn_rpe_fwd(ptr(qkv), ptr(cu), ptr(gc), ptr(tab), int(pos_bnd), cu.numel() - 1, T, H, int(max_seqlen),
-                                 float(softmax_scale), dtype_code(qkv), ptr(out), ptr(lse), stream_ptr()), "ptc_attn_rpe_fwd")
+    lib().ptc_attn_rpe_fwd(ptr(qkv), ptr(cu), ptr(gc), ptr(tab), int(pos_bnd), cu.numel() - 1, T, H, int(max_seqlen),
+                           float(softmax_scale), dtype_code(qkv), ptr(out), ptr(lse), stream_ptr())
     return out, lse
 
 
@@ -1034,9 +1022,9 @@ def attn_rpe_bwd(qkv, out, dout, lse, cu_seqlens, max_seqlen: int, softmax_scale
     dtab = torch.empty_like(tab)
     nbytes = lib().ptc_attn_rpe_bwd_workspace_bytes(T, H, int(pos_bnd))
     ws = _ws(nbytes, qkv.device)
-    check(lib().ptc_attn_rpe_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), ptr(gc), ptr(tab), int(pos_bnd), cu.numel() - 1,
-                                 T, H, int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(dtab), ptr(ws), nbytes,
-                                 stream_ptr()), "ptc_attn_rpe_bwd")
+    lib().ptc_attn_rpe_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), ptr(gc), ptr(tab), int(pos_bnd), cu.numel() - 1,
+                           T, H, int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(dtab), ptr(ws), nbytes,
+                           stream_ptr())
     return dqkv, dtab
 
 
@@ -1050,7 +1038,7 @@ def coord_max(grid_coord: torch.Tensor) -> torch.Tensor:
         raise PtcoreError("grid_coord must be int32/int64 [N,3]")
     gc = grid_coord.contiguous()
     out = torch.empty(3, dtype=torch.int64, device=gc.device)
-    check(lib().ptc_coord_max(ptr(gc), int(gc.dtype == torch.int64), gc.shape[0], ptr(out), stream_ptr()), "ptc_coord_max")
+    lib().ptc_coord_max(ptr(gc), int(gc.dtype == torch.int64), gc.shape[0], ptr(out), stream_ptr())
     return out
 
 
@@ -1075,8 +1063,8 @@ def cross_entropy_fwd(logits: torch.Tensor, target: torch.Tensor, ignore_index: 
     nb = lib().ptc_cross_entropy_partials(n)
     lse = torch.empty(n, dtype=torch.float32, device=lg.device)
     partial = torch.empty((nb, 2), dtype=torch.float32, device=lg.device)
-    check(lib().ptc_cross_entropy_fwd(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), int(ignore_index), ptr(lse),
-                                      ptr(partial), stream_ptr()), "ptc_cross_entropy_fwd")
+    lib().ptc_cross_entropy_fwd(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), int(ignore_index), ptr(lse),
+                                ptr(partial), stream_ptr())
     tot = partial.sum(0)   # fixed-order tree reduction of <= N/256 partials: deterministic
     return tot[0], tot[1], lse
 
@@ -1087,8 +1075,8 @@ def cross_entropy_bwd(logits: torch.Tensor, target: torch.Tensor, lse: torch.Ten
     lg, rs = _rows_view(logits)
     n, c = lg.shape
     out = torch.empty((n, c), dtype=lg.dtype, device=lg.device)
-    check(lib().ptc_cross_entropy_bwd(ptr(lg), rs, ptr(target.contiguous()), ptr(lse), ptr(scale.reshape(1).float().contiguous()),
-                                      n, c, dtype_code(lg), int(ignore_index), ptr(out), c, stream_ptr()), "ptc_cross_entropy_bwd")
+    lib().ptc_cross_entropy_bwd(ptr(lg), rs, ptr(target.contiguous()), ptr(lse), ptr(scale.reshape(1).float().contiguous()),
+                                n, c, dtype_code(lg), int(ignore_index), ptr(out), c, stream_ptr())
     return out
 
 
@@ -1134,15 +1122,15 @@ def criteria_rows_fwd(logits: torch.Tensor, target: torch.Tensor, spec: Criteria
     nb, pw = lib().ptc_criteria_partials(n), lib().ptc_criteria_partial_width(c, spec.flags)
     lse = torch.empty(n, dtype=torch.float32, device=lg.device)
     partial = torch.empty((nb, pw), dtype=torch.float32, device=lg.device)
-    check(lib().ptc_criteria_fwd(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), spec.ignore_index, spec.flags,
-                                 ptr(spec.ce_weight), float(spec.ce_eps), ptr(spec.focal_alpha_vec), float(spec.focal_alpha),
-                                 float(spec.focal_gamma), int(spec.dice_exp), ptr(lse), ptr(partial), stream_ptr()), "ptc_criteria_fwd")
+    lib().ptc_criteria_fwd(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), spec.ignore_index, spec.flags,
+                           ptr(spec.ce_weight), float(spec.ce_eps), ptr(spec.focal_alpha_vec), float(spec.focal_alpha),
+                           float(spec.focal_gamma), int(spec.dice_exp), ptr(lse), ptr(partial), stream_ptr())
     sums = partial.sum(0, dtype=torch.float64)       # fixed-order reduction of <= N/256 partial rows: deterministic
     out = torch.empty(4, dtype=torch.float32, device=lg.device)
     coef = torch.empty(4 + 2 * c, dtype=torch.float32, device=lg.device)
-    check(lib().ptc_criteria_finish(ptr(sums), c, spec.flags, spec.ignore_index, ptr(spec.ce_weight), int(bool(spec.ce_sum)),
-                                    float(spec.ce_lw), float(spec.focal_lw), float(spec.dice_lw), float(spec.dice_smooth),
-                                    int(spec.dice_exp), ptr(out), ptr(coef), stream_ptr()), "ptc_criteria_finish")
+    lib().ptc_criteria_finish(ptr(sums), c, spec.flags, spec.ignore_index, ptr(spec.ce_weight), int(bool(spec.ce_sum)),
+                              float(spec.ce_lw), float(spec.focal_lw), float(spec.dice_lw), float(spec.dice_smooth),
+                              int(spec.dice_exp), ptr(out), ptr(coef), stream_ptr())
     return out, lse, coef
 
 
@@ -1154,10 +1142,10 @@ def criteria_rows_bwd(logits: torch.Tensor, target: torch.Tensor, lse: torch.Ten
     n, c = lg.shape
     _criteria_check(spec, lg)
     out = torch.empty((n, c), dtype=lg.dtype, device=lg.device)
-    check(lib().ptc_criteria_bwd(ptr(lg), rs, ptr(target.contiguous()), ptr(lse), ptr(coef), ptr(grad.reshape(1).float().contiguous()),
-                                 n, c, dtype_code(lg), spec.ignore_index, spec.flags, ptr(spec.ce_weight), float(spec.ce_eps),
-                                 ptr(spec.focal_alpha_vec), float(spec.focal_alpha), float(spec.focal_gamma), int(spec.dice_exp),
-                                 ptr(out), stream_ptr()), "ptc_criteria_bwd")
+    lib().ptc_criteria_bwd(ptr(lg), rs, ptr(target.contiguous()), ptr(lse), ptr(coef), ptr(grad.reshape(1).float().contiguous()),
+                           n, c, dtype_code(lg), spec.ignore_index, spec.flags, ptr(spec.ce_weight), float(spec.ce_eps),
+                           ptr(spec.focal_alpha_vec), float(spec.focal_alpha), float(spec.focal_gamma), int(spec.dice_exp),
+                           ptr(out), stream_ptr())
     return out
 
 
@@ -1207,8 +1195,8 @@ def lovasz_present(target: torch.Tensor, num_classes: int, ignore_index: int) ->
     tg = target.contiguous()
     buf = torch.empty(3 * c + 1, dtype=torch.int32, device=tg.device)
     count, row_of, class_of, n_present = buf[:c], buf[c:2 * c], buf[2 * c:3 * c], buf[3 * c:]
-    check(lib().ptc_lovasz_present(ptr(tg), tg.shape[0], c, int(ignore_index), ptr(count), ptr(row_of), ptr(class_of), ptr(n_present),
-                                   stream_ptr()), "ptc_lovasz_present")
+    lib().ptc_lovasz_present(ptr(tg), tg.shape[0], c, int(ignore_index), ptr(count), ptr(row_of), ptr(class_of), ptr(n_present),
+                             stream_ptr())
     if tg.is_cuda:
         host = torch.empty(1, dtype=torch.int32, pin_memory=True)
         host.copy_(n_present, non_blocking=True)
@@ -1242,8 +1230,8 @@ def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, ignore_index: int
     ws = _ws(nbytes, lg.device)
     loss = torch.empty((), dtype=torch.float32, device=lg.device)
     dlogits = torch.empty((n, c), dtype=torch.float32, device=lg.device)
-    check(lib().ptc_lovasz_softmax(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), int(ignore_index), ptr(loss),
-                                   ptr(dlogits), ptr(ws), nbytes, stream_ptr()), "ptc_lovasz_softmax")
+    lib().ptc_lovasz_softmax(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), int(ignore_index), ptr(loss),
+                             ptr(dlogits), ptr(ws), nbytes, stream_ptr())
     return loss, dlogits
 
 
@@ -1265,9 +1253,9 @@ def _lovasz_softmax_rows(lg, rs, target, ignore_index, present):
     ws = _ws(nbytes, lg.device)
     loss = torch.empty((), dtype=torch.float32, device=lg.device)
     dlogits = torch.empty((n, c), dtype=torch.float32, device=lg.device)
-    check(lib().ptc_lovasz_softmax_rows(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), int(ignore_index), ptr(present.class_count),
-                                        ptr(present.row_of), ptr(present.class_of), ptr(present.n_present), rows, ptr(loss), ptr(dlogits),
-                                        ptr(ws), nbytes, stream_ptr()), "ptc_lovasz_softmax_rows")
+    lib().ptc_lovasz_softmax_rows(ptr(lg), rs, ptr(target.contiguous()), n, c, dtype_code(lg), int(ignore_index), ptr(present.class_count),
+                                  ptr(present.row_of), ptr(present.class_of), ptr(present.n_present), rows, ptr(loss), ptr(dlogits),
+                                  ptr(ws), nbytes, stream_ptr())
     return loss, dlogits
 
 
@@ -1280,8 +1268,7 @@ ACT_CODES = {"none": 0, "gelu": 1, "relu": 2}
 def batch_norm_supported(c: int, dtype: torch.dtype) -> bool:
     if dtype not in (torch.float32, torch.bfloat16, torch.float16):
         return False
-    code = {torch.float32: _lib.PTC_F32, torch.float16: _lib.PTC_F16, torch.bfloat16: _lib.PTC_BF16}[dtype]
-    return bool(lib().ptc_batch_norm_supported(int(c), code))
+    return bool(lib().ptc_batch_norm_supported(int(c), _DT[dtype]))
 
 
 def batch_norm_act_fwd(x, gamma, beta, running_mean, running_var, training: bool, momentum: float, eps: float, act: str,
@@ -1307,14 +1294,13 @@ def batch_norm_act_fwd(x, gamma, beta, running_mean, running_var, training: bool
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise PtcoreError("running statistics must be contiguous fp32")
     if res is not None:
-        check(lib().ptc_batch_norm_add_act_fwd(ptr(x), ptr(res), n, c, dtype_code(x), ptr(g), ptr(b), float(eps), float(momentum),
-                                               int(bool(training)), ptr(running_mean), ptr(running_var), ACT_CODES[act], ptr(y),
-                                               dtype_code(y), ptr(mean), ptr(rstd), ptr(ws), nbytes, stream_ptr()),
-              "ptc_batch_norm_add_act_fwd")
+        lib().ptc_batch_norm_add_act_fwd(ptr(x), ptr(res), n, c, dtype_code(x), ptr(g), ptr(b), float(eps), float(momentum),
+                                         int(bool(training)), ptr(running_mean), ptr(running_var), ACT_CODES[act], ptr(y),
+                                         dtype_code(y), ptr(mean), ptr(rstd), ptr(ws), nbytes, stream_ptr())
         return y, mean, rstd
-    check(lib().ptc_batch_norm_act_fwd(ptr(x), n, c, dtype_code(x), ptr(g), ptr(b), float(eps), float(momentum), int(bool(training)),
-                                       ptr(running_mean), ptr(running_var), ACT_CODES[act], ptr(y), dtype_code(y), ptr(mean),
-                                       ptr(rstd), ptr(ws), nbytes, stream_ptr()), "ptc_batch_norm_act_fwd")
+    lib().ptc_batch_norm_act_fwd(ptr(x), n, c, dtype_code(x), ptr(g), ptr(b), float(eps), float(momentum), int(bool(training)),
+                                 ptr(running_mean), ptr(running_var), ACT_CODES[act], ptr(y), dtype_code(y), ptr(mean),
+                                 ptr(rstd), ptr(ws), nbytes, stream_ptr())
     return y, mean, rstd
 
 
@@ -1333,13 +1319,12 @@ def batch_norm_act_bwd(dy, x, gamma, beta, mean, rstd, training: bool, act: str,
     if res is not None:
         res = res.contiguous()
         dres = torch.empty_like(x)
-        check(lib().ptc_batch_norm_add_act_bwd(ptr(dy), dtype_code(dy), ptr(x), ptr(res), dtype_code(x), ptr(g), ptr(b), ptr(mean), ptr(rstd), n, c,
-                                               int(bool(training)), ACT_CODES[act], ptr(dx), ptr(dres), ptr(dg), ptr(db), ptr(ws), nbytes,
-                                               stream_ptr()), "ptc_batch_norm_add_act_bwd")
+        lib().ptc_batch_norm_add_act_bwd(ptr(dy), dtype_code(dy), ptr(x), ptr(res), dtype_code(x), ptr(g), ptr(b), ptr(mean), ptr(rstd), n, c,
+                                         int(bool(training)), ACT_CODES[act], ptr(dx), ptr(dres), ptr(dg), ptr(db), ptr(ws), nbytes,
+                                         stream_ptr())
         return dx, dg, db, dres
-    check(lib().ptc_batch_norm_act_bwd(ptr(dy), dtype_code(dy), ptr(x), dtype_code(x), ptr(g), ptr(b), ptr(mean), ptr(rstd), n, c,
-                                       int(bool(training)), ACT_CODES[act], ptr(dx), ptr(dg), ptr(db), ptr(ws), nbytes, stream_ptr()),
-          "ptc_batch_norm_act_bwd")
+    lib().ptc_batch_norm_act_bwd(ptr(dy), dtype_code(dy), ptr(x), dtype_code(x), ptr(g), ptr(b), ptr(mean), ptr(rstd), n, c,
+                                 int(bool(training)), ACT_CODES[act], ptr(dx), ptr(dg), ptr(db), ptr(ws), nbytes, stream_ptr())
     return dx, dg, db
 
 
@@ -1355,15 +1340,14 @@ def column_sum(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty(c, dtype=torch.float32, device=x.device)
     nbytes = lib().ptc_batch_norm_workspace_bytes(n, c)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    check(lib().ptc_column_sum(ptr(x), n, c, dtype_code(x), ptr(out), ptr(ws), nbytes, stream_ptr()), "ptc_column_sum")
+    lib().ptc_column_sum(ptr(x), n, c, dtype_code(x), ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
 def linear_supported_ex(c_in: int, c_out: int, dtype: torch.dtype) -> bool:
     if dtype not in (torch.bfloat16, torch.float16):
         return False
-    code = _lib.PTC_F16 if dtype == torch.float16 else _lib.PTC_BF16
-    return bool(lib().ptc_linear_supported_ex(int(c_in), int(c_out), code))
+    return bool(lib().ptc_linear_supported_ex(int(c_in), int(c_out), _DT[dtype]))
 
 
 def linear_gelu_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]):
@@ -1375,8 +1359,7 @@ def linear_gelu_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
     h = torch.empty((n, c_out), dtype=x.dtype, device=x.device)
     a = torch.empty((n, c_out), dtype=x.dtype, device=x.device)
     b = None if bias is None else bias.to(torch.float32).contiguous()
-    check(lib().ptc_linear_fwd_ex(ptr(x), n, ptr(weight), ptr(b), c_in, c_out, dtype_code(x), 1, 0, ptr(h), ptr(a), stream_ptr()),
-          "ptc_linear_fwd_ex")
+    lib().ptc_linear_fwd_ex(ptr(x), n, ptr(weight), ptr(b), c_in, c_out, dtype_code(x), 1, 0, ptr(h), ptr(a), stream_ptr())
     return h, a
 
 
@@ -1387,8 +1370,7 @@ def linear_gelu_bwd_input(g: torch.Tensor, weight_t: torch.Tensor, h: torch.Tens
     n, c_in = g.shape
     c_out = weight_t.shape[0]
     out = torch.empty((n, c_out), dtype=g.dtype, device=g.device)
-    check(lib().ptc_linear_fwd_ex(ptr(g), n, ptr(weight_t), 0, c_in, c_out, dtype_code(g), 2, ptr(h), ptr(out), 0, stream_ptr()),
-          "ptc_linear_fwd_ex")
+    lib().ptc_linear_fwd_ex(ptr(g), n, ptr(weight_t), 0, c_in, c_out, dtype_code(g), 2, ptr(h), ptr(out), 0, stream_ptr())
     return out
 
 
@@ -1396,7 +1378,7 @@ def mlp_supported(c: int, dtype: torch.dtype) -> bool:
     """the one-kernel MLP (csrc/mlp.hip): C = 32 | 64 (hidden 4 C), bf16 / f16"""
     if dtype not in (torch.bfloat16, torch.float16):
         return False
-    return bool(lib().ptc_mlp_supported(int(c), _lib.PTC_F16 if dtype == torch.float16 else _lib.PTC_BF16))
+    return bool(lib().ptc_mlp_supported(int(c), _DT[dtype]))
 
 
 def mlp_fwd(x, w1, b1, w2, b2, a=None, row_scale=None, want_y=True):
@@ -1411,7 +1393,7 @@ def mlp_fwd(x, w1, b1, w2, b2, a=None, row_scale=None, want_y=True):
     b2 = None if b2 is None else b2.to(torch.float32).contiguous()
     if a is None:
         y = torch.empty((n, c), dtype=x.dtype, device=x.device)
-        check(lib().ptc_mlp_fwd(ptr(x), n, c, dtype_code(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), 0, 0, 0, ptr(y), stream_ptr()), "ptc_mlp_fwd")
+        lib().ptc_mlp_fwd(ptr(x), n, c, dtype_code(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), 0, 0, 0, ptr(y), stream_ptr())
         return y
     if a.dtype != torch.float32 or tuple(a.shape) != (n, c):
         raise PtcoreError("mlp_fwd: the residual stream must be fp32 [N, C]")
@@ -1419,7 +1401,7 @@ def mlp_fwd(x, w1, b1, w2, b2, a=None, row_scale=None, want_y=True):
     rs = None if row_scale is None else row_scale.to(torch.float32).contiguous()
     z = torch.empty((n, c), dtype=torch.float32, device=x.device)
     y = torch.empty((n, c), dtype=x.dtype, device=x.device) if want_y else None
-    check(lib().ptc_mlp_fwd(ptr(x), n, c, dtype_code(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(a), ptr(rs), ptr(z), ptr(y), stream_ptr()), "ptc_mlp_fwd")
+    lib().ptc_mlp_fwd(ptr(x), n, c, dtype_code(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(a), ptr(rs), ptr(z), ptr(y), stream_ptr())
     return z, y
 
 
@@ -1439,22 +1421,21 @@ def mlp_bwd(dm, x, w1, b1, w2t, want_b1=True, want_b2=True):
     db2 = torch.empty((c,), dtype=torch.float32, device=x.device) if want_b2 else None
     nbytes = lib().ptc_mlp_bwd_workspace_bytes(n, c)
     ws = _ws(nbytes, x.device)
-    check(lib().ptc_mlp_bwd(ptr(dm), ptr(x), n, c, dtype_code(x), ptr(w1), ptr(b1), ptr(w2t), ptr(dx), ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), ptr(ws), nbytes,
-                            stream_ptr()), "ptc_mlp_bwd")
+    lib().ptc_mlp_bwd(ptr(dm), ptr(x), n, c, dtype_code(x), ptr(w1), ptr(b1), ptr(w2t), ptr(dx), ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), ptr(ws), nbytes,
+                      stream_ptr())
     return dx, dw1, db1, dw2, db2
 
 
 def weight_layouts(desc: torch.Tensor, prefix: torch.Tensor, n: int, total: int) -> None:
     """functional._CastCache: rewrite every backward-pass weight layout described by desc [n,6] / prefix [n+1] (device int64)."""
     require_cuda(desc, prefix)
-    check(lib().ptc_weight_layouts(ptr(desc), ptr(prefix), int(n), int(total), stream_ptr()), "ptc_weight_layouts")
+    lib().ptc_weight_layouts(ptr(desc), ptr(prefix), int(n), int(total), stream_ptr())
 
 
 def cast_many(desc: torch.Tensor, prefix: torch.Tensor, n: int, total_units: int, dst_dtype: torch.dtype) -> None:
     """functional._CastCache: refresh the 16-bit shadows described by desc [n,3] / prefix [n+1] (device int64) from their fp32 weights."""
     require_cuda(desc, prefix)
-    code = {torch.bfloat16: _lib.PTC_BF16, torch.float16: _lib.PTC_F16}[dst_dtype]
-    check(lib().ptc_cast_many(ptr(desc), ptr(prefix), int(n), int(total_units), code, stream_ptr()), "ptc_cast_many")
+    lib().ptc_cast_many(ptr(desc), ptr(prefix), int(n), int(total_units), _DT[dst_dtype], stream_ptr())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1482,8 +1463,8 @@ def pair_dot_fwd(q, k, i0, i1, table_q, table_k, rel_idx, with_qk: bool) -> torc
     for nm, t in (("table_q", table_q), ("table_k", table_k)):
         _p2_check(nm, t, (t.shape[0], H, d, 3) if t is not None else None)
     out = torch.empty((M, H), dtype=torch.float32, device=q.device)
-    check(lib().ptc_pair_dot_fwd(ptr(q), ptr(k), ptr(i0), ptr(i1), ptr(table_q), ptr(table_k), ptr(rel_idx), int(bool(with_qk)), M, H, d,
-                                 ptr(out), stream_ptr()), "ptc_pair_dot_fwd")
+    lib().ptc_pair_dot_fwd(ptr(q), ptr(k), ptr(i0), ptr(i1), ptr(table_q), ptr(table_k), ptr(rel_idx), int(bool(with_qk)), M, H, d,
+                           ptr(out), stream_ptr())
     return out
 
 
@@ -1501,9 +1482,8 @@ def pair_dot_bwd(g, q, k, i0, offsets, i1, table_q, table_k, rel_idx, with_qk: b
     dk = torch.empty_like(k) if (want_k and k is not None) else None
     dtq = torch.empty_like(table_q) if (want_tq and table_q is not None) else None
     dtk = torch.empty_like(table_k) if (want_tk and table_k is not None) else None
-    check(lib().ptc_pair_dot_bwd(ptr(g), ptr(q), ptr(k), ptr(i0), ptr(offsets), ptr(i1), ptr(table_q), ptr(table_k), ptr(rel_idx),
-                                 int(bool(with_qk)), M, Nq, Nk, L, H, d, ptr(dq), ptr(dk), ptr(dtq), ptr(dtk), stream_ptr()),
-          "ptc_pair_dot_bwd")
+    lib().ptc_pair_dot_bwd(ptr(g), ptr(q), ptr(k), ptr(i0), ptr(offsets), ptr(i1), ptr(table_q), ptr(table_k), ptr(rel_idx),
+                           int(bool(with_qk)), M, Nq, Nk, L, H, d, ptr(dq), ptr(dk), ptr(dtq), ptr(dtk), stream_ptr())
     return dq, dk, dtq, dtk
 
 
@@ -1521,8 +1501,8 @@ def pair_aggregate_fwd(attn, v, i0, offsets, i1, table_v, rel_idx, n_q: int) -> 
     if offsets is not None and offsets.numel() != int(n_q) + 1:
         raise PtcoreError(f"offsets must have {int(n_q) + 1} entries, got {offsets.numel()}")
     out = torch.empty((int(n_q), H, d), dtype=torch.float32, device=v.device)
-    check(lib().ptc_pair_aggregate_fwd(ptr(attn), ptr(v), ptr(i0), ptr(offsets), ptr(i1), ptr(table_v), ptr(rel_idx), M, int(n_q), H, d,
-                                       ptr(out), stream_ptr()), "ptc_pair_aggregate_fwd")
+    lib().ptc_pair_aggregate_fwd(ptr(attn), ptr(v), ptr(i0), ptr(offsets), ptr(i1), ptr(table_v), ptr(rel_idx), M, int(n_q), H, d,
+                                 ptr(out), stream_ptr())
     return out
 
 
@@ -1535,8 +1515,8 @@ def pair_aggregate_bwd(g, attn, v, i0, i1, table_v, rel_idx, want_attn=True, wan
     da = torch.empty_like(attn) if want_attn else None
     dv = torch.empty_like(v) if want_v else None
     dtv = torch.empty_like(table_v) if (want_tv and table_v is not None) else None
-    check(lib().ptc_pair_aggregate_bwd(ptr(g), ptr(attn), ptr(v), ptr(i0), ptr(i1), ptr(table_v), ptr(rel_idx), M, Nv, L, H, d, ptr(da),
-                                       ptr(dv), ptr(dtv), stream_ptr()), "ptc_pair_aggregate_bwd")
+    lib().ptc_pair_aggregate_bwd(ptr(g), ptr(attn), ptr(v), ptr(i0), ptr(i1), ptr(table_v), ptr(rel_idx), M, Nv, L, H, d, ptr(da),
+                                 ptr(dv), ptr(dtv), stream_ptr())
     return da, dv, dtv
 
 
@@ -1579,14 +1559,14 @@ def grid_clusters(indices: torch.Tensor, sizes: Sequence[int], spatial_shape: Se
     ws = _ws(nbytes, dev)
     sz = (ctypes.c_int * L)(*[int(s) for s in sizes])
     shp = (ctypes.c_int * 3)(*[int(s) for s in spatial_shape])
-    check(lib().ptc_grid_cluster_count(ptr(ind), n, ctypes.cast(sz, ctypes.c_void_p), L, ctypes.cast(shp, ctypes.c_void_p), int(batch_size),
-                                       ptr(order), ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr()), "ptc_grid_cluster_count")
+    lib().ptc_grid_cluster_count(ptr(ind), n, ctypes.cast(sz, ctypes.c_void_p), L, ctypes.cast(shp, ctypes.c_void_p), int(batch_size),
+                                 ptr(order), ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr())
     n_cluster = [int(v) for v in ncl.tolist()]
     indptr = []
     for l in range(L):
         ip = torch.empty(n_cluster[l] + 1, dtype=torch.int64, device=dev)
         head = torch.empty(n_cluster[l], dtype=torch.int64, device=dev)
-        check(lib().ptc_pool_maps_fill(ptr(order[l]), ptr(cluster[l]), n, n_cluster[l], ptr(ip), ptr(head), stream_ptr()), "ptc_pool_maps_fill")
+        lib().ptc_pool_maps_fill(ptr(order[l]), ptr(cluster[l]), n, n_cluster[l], ptr(ip), ptr(head), stream_ptr())
         indptr.append(ip)
     return GridClusters(list(order.unbind(0)), list(cluster.unbind(0)), indptr, n_cluster)
 
@@ -1610,9 +1590,8 @@ def cluster_center(xs: Sequence[torch.Tensor], gc: GridClusters) -> list:
     perm, ip, _, ncl = gc._arrays()
     xa = (ctypes.c_void_p * L)(*[ptr(x) for x in xs])
     ya = (ctypes.c_void_p * L)(*[ptr(y) for y in ys])
-    check(lib().ptc_cluster_center(ctypes.cast(xa, ctypes.c_void_p), ctypes.cast(perm, ctypes.c_void_p), ctypes.cast(ip, ctypes.c_void_p),
-                                   ctypes.cast(ncl, ctypes.c_void_p), L, n, c, dtype_code(xs[0]), ctypes.cast(ya, ctypes.c_void_p), stream_ptr()),
-          "ptc_cluster_center")
+    lib().ptc_cluster_center(ctypes.cast(xa, ctypes.c_void_p), ctypes.cast(perm, ctypes.c_void_p), ctypes.cast(ip, ctypes.c_void_p),
+                             ctypes.cast(ncl, ctypes.c_void_p), L, n, c, dtype_code(xs[0]), ctypes.cast(ya, ctypes.c_void_p), stream_ptr())
     return ys
 
 
@@ -1636,8 +1615,8 @@ def cluster_agg_fwd(us: Sequence[torch.Tensor], vs: Sequence[torch.Tensor], a: t
     ua = (ctypes.c_void_p * L)(*[ptr(t) for t in us])
     va = (ctypes.c_void_p * L)(*[ptr(t) for t in vs])
     V = ctypes.c_void_p
-    check(lib().ptc_cluster_agg_fwd(ctypes.cast(ua, V), ctypes.cast(va, V), ptr(a), ctypes.cast(perm, V), ctypes.cast(ip, V), ctypes.cast(cl, V),
-                                    ctypes.cast(ncl, V), L, n, c, dtype_code(a), ptr(out), ptr(state), sbytes, stream_ptr()), "ptc_cluster_agg_fwd")
+    lib().ptc_cluster_agg_fwd(ctypes.cast(ua, V), ctypes.cast(va, V), ptr(a), ctypes.cast(perm, V), ctypes.cast(ip, V), ctypes.cast(cl, V),
+                              ctypes.cast(ncl, V), L, n, c, dtype_code(a), ptr(out), ptr(state), sbytes, stream_ptr())
     return out, state
 
 
@@ -1658,10 +1637,9 @@ def cluster_agg_bwd(us, vs, a, dout: torch.Tensor, state: torch.Tensor, gc: Grid
     perm, ip, cl, ncl = gc._arrays()
     V = ctypes.c_void_p
     keep = [(V * L)(*[ptr(t) for t in ts]) for ts in (us, vs, du, dv)]
-    check(lib().ptc_cluster_agg_bwd(ctypes.cast(keep[0], V), ctypes.cast(keep[1], V), ptr(a), ptr(dout), ctypes.cast(perm, V), ctypes.cast(ip, V),
-                                    ctypes.cast(cl, V), ctypes.cast(ncl, V), L, n, c, dtype_code(a), ptr(state), state.numel(),
-                                    ctypes.cast(keep[2], V), ctypes.cast(keep[3], V), ptr(da), ptr(ws), wbytes, stream_ptr()),
-          "ptc_cluster_agg_bwd")
+    lib().ptc_cluster_agg_bwd(ctypes.cast(keep[0], V), ctypes.cast(keep[1], V), ptr(a), ptr(dout), ctypes.cast(perm, V), ctypes.cast(ip, V),
+                              ctypes.cast(cl, V), ctypes.cast(ncl, V), L, n, c, dtype_code(a), ptr(state), state.numel(),
+                              ctypes.cast(keep[2], V), ctypes.cast(keep[3], V), ptr(da), ptr(ws), wbytes, stream_ptr())
     return du, dv, da
 
 
@@ -1687,16 +1665,15 @@ def pg_ball_query(xyz: torch.Tensor, batch_idxs: torch.Tensor, n_batch: int, rad
     total = torch.empty(2, dtype=torch.int64, device=dev)
     nbytes = lib().ptc_pg_ball_query_workspace_bytes(n)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_pg_ball_query_count(ptr(x), ptr(b), n, int(n_batch), float(radius), ptr(start_len), ptr(total), ptr(ws), nbytes,
-                                        stream_ptr()), "ptc_pg_ball_query_count")
+    lib().ptc_pg_ball_query_count(ptr(x), ptr(b), n, int(n_batch), float(radius), ptr(start_len), ptr(total), ptr(ws), nbytes,
+                                  stream_ptr())
     n_active, n_trunc = [int(v) for v in total.tolist()]
     if n_active >= 1 << 31:
         raise PtcoreError(f"pg_ball_query: {n_active} neighbour entries exceed the int32 index range")
     idx = torch.empty(n_active, dtype=torch.int32, device=dev)
     if n_active == 0:
         return idx, start_len, n_trunc
-    check(lib().ptc_pg_ball_query_fill(ptr(x), n, float(radius), ptr(start_len), ptr(idx), ptr(ws), nbytes, stream_ptr()),
-          "ptc_pg_ball_query_fill")
+    lib().ptc_pg_ball_query_fill(ptr(x), n, float(radius), ptr(start_len), ptr(idx), ptr(ws), nbytes, stream_ptr())
     return idx, start_len, n_trunc
 
 
@@ -1715,12 +1692,11 @@ def pg_cluster(label: torch.Tensor, idx: torch.Tensor, start_len: torch.Tensor, 
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     nbytes = lib().ptc_pg_cluster_workspace_bytes(n)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_pg_cluster_count(ptr(lab), ptr(ix), ptr(sl), n, int(threshold), int(bool(skip_negative)), ptr(counts), ptr(ws), nbytes, stream_ptr()),
-          "ptc_pg_cluster_count")
+    lib().ptc_pg_cluster_count(ptr(lab), ptr(ix), ptr(sl), n, int(threshold), int(bool(skip_negative)), ptr(counts), ptr(ws), nbytes, stream_ptr())
     n_cluster, n_sum = [int(v) for v in counts.tolist()]
     cidx = torch.empty((n_sum, 2), dtype=torch.int32, device=dev)
     coff = torch.empty(n_cluster + 1, dtype=torch.int32, device=dev)
-    check(lib().ptc_pg_cluster_fill(n, n_cluster, n_sum, ptr(cidx), ptr(coff), ptr(ws), nbytes, stream_ptr()), "ptc_pg_cluster_fill")
+    lib().ptc_pg_cluster_fill(n, n_cluster, n_sum, ptr(cidx), ptr(coff), ptr(ws), nbytes, stream_ptr())
     return cidx, coff
 
 
@@ -1738,9 +1714,9 @@ def pg_proposal_scores(logits: torch.Tensor, label: torch.Tensor, cluster_idxs: 
     cls = torch.empty(k, dtype=torch.int32, device=dev)
     score = torch.empty(k, dtype=torch.float32, device=dev)
     pm = None if point_map is None else point_map.to(torch.int64).contiguous()
-    check(lib().ptc_pg_proposal_scores(ptr(lg), dtype_code(lg), lg.shape[0], lg.shape[1], ptr(label.to(torch.int32).contiguous()),
-                                       ptr(cluster_idxs.contiguous()), ptr(cluster_offsets.contiguous()), k, ptr(pm), ptr(count), ptr(cls),
-                                       ptr(score), stream_ptr()), "ptc_pg_proposal_scores")
+    lib().ptc_pg_proposal_scores(ptr(lg), dtype_code(lg), lg.shape[0], lg.shape[1], ptr(label.to(torch.int32).contiguous()),
+                                 ptr(cluster_idxs.contiguous()), ptr(cluster_offsets.contiguous()), k, ptr(pm), ptr(count), ptr(cls),
+                                 ptr(score), stream_ptr())
     return count, cls, score
 
 
@@ -1750,8 +1726,8 @@ def pg_proposal_masks(cluster_idxs: torch.Tensor, row: torch.Tensor, n_rows: int
     out = torch.empty((int(n_rows), int(n_points)), dtype=torch.int32, device=cluster_idxs.device)
     pm = None if point_map is None else point_map.to(torch.int64).contiguous()
     ci = cluster_idxs.contiguous()
-    check(lib().ptc_pg_proposal_masks(ptr(ci), ci.shape[0], ptr(row.to(torch.int64).contiguous()), ptr(pm), int(n_points), int(n_rows),
-                                      ptr(out), stream_ptr()), "ptc_pg_proposal_masks")
+    lib().ptc_pg_proposal_masks(ptr(ci), ci.shape[0], ptr(row.to(torch.int64).contiguous()), ptr(pm), int(n_points), int(n_rows),
+                                ptr(out), stream_ptr())
     return out
 
 
@@ -1774,8 +1750,8 @@ def pg_bias_loss_fwd(bias_pred, coord, centroid, instance, ignore_index: int) ->
     out = torch.empty(3, dtype=torch.float32, device=bp.device)
     nbytes = lib().ptc_pg_bias_loss_workspace_bytes(n)
     ws = _ws(nbytes, bp.device)
-    check(lib().ptc_pg_bias_loss_fwd(ptr(bp), dtype_code(bp), ptr(c), ptr(g), ptr(i), n, int(ignore_index), ptr(out), ptr(ws), nbytes,
-                                     stream_ptr()), "ptc_pg_bias_loss_fwd")
+    lib().ptc_pg_bias_loss_fwd(ptr(bp), dtype_code(bp), ptr(c), ptr(g), ptr(i), n, int(ignore_index), ptr(out), ptr(ws), nbytes,
+                               stream_ptr())
     return out
 
 
@@ -1783,8 +1759,8 @@ def pg_bias_loss_bwd(bias_pred, coord, centroid, instance, ignore_index: int, do
     """d bias_pred [n, 3] (bias_pred's dtype) from dout [2] fp32 = (d l1, d cos)"""
     bp, c, g, i, n = _pg_bias_args(bias_pred, coord, centroid, instance)
     d = torch.empty_like(bp)
-    check(lib().ptc_pg_bias_loss_bwd(ptr(bp), dtype_code(bp), ptr(c), ptr(g), ptr(i), n, int(ignore_index),
-                                     ptr(dout.float().contiguous()), ptr(fwd_out), ptr(d), stream_ptr()), "ptc_pg_bias_loss_bwd")
+    lib().ptc_pg_bias_loss_bwd(ptr(bp), dtype_code(bp), ptr(c), ptr(g), ptr(i), n, int(ignore_index),
+                               ptr(dout.float().contiguous()), ptr(fwd_out), ptr(d), stream_ptr())
     return d
 
 
@@ -1817,8 +1793,8 @@ def msc_match(k: int, max_radius: float, xyz, offset, new_xyz, new_offset):
     stats = torch.empty(2, dtype=torch.int32, device=dev)
     nbytes = lib().ptc_msc_match_workspace_bytes(n)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_msc_match(ptr(x), ptr(off), ptr(q), ptr(noff), off.numel(), n, m, int(k), float(max_radius), ptr(count), ptr(cand),
-                              ptr(stats), ptr(ws), nbytes, stream_ptr()), "ptc_msc_match")
+    lib().ptc_msc_match(ptr(x), ptr(off), ptr(q), ptr(noff), off.numel(), n, m, int(k), float(max_radius), ptr(count), ptr(cand),
+                        ptr(stats), ptr(ws), nbytes, stream_ptr())
     return count, cand, stats
 
 
@@ -1834,7 +1810,7 @@ def msc_select(count: torch.Tensor, cand: torch.Tensor, r: torch.Tensor) -> torc
     out = torch.empty((rr.numel(), 2), dtype=torch.int64, device=cd.device)
     nbytes = lib().ptc_msc_select_workspace_bytes(m)
     ws = _ws(nbytes, cd.device)
-    check(lib().ptc_msc_select(ptr(cnt), ptr(cd), m, k, ptr(rr), rr.numel(), ptr(out), ptr(ws), nbytes, stream_ptr()), "ptc_msc_select")
+    lib().ptc_msc_select(ptr(cnt), ptr(cd), m, k, ptr(rr), rr.numel(), ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -1850,8 +1826,8 @@ def msc_patch_rank(cell1, offset1, cell2, offset2):
     patch_num = torch.empty(1, dtype=torch.int64, device=dev)
     nbytes = lib().ptc_msc_patch_workspace_bytes(n1 + n2)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_msc_patch_rank(ptr(c1), ptr(o1), n1, ptr(c2), ptr(o2), n2, o1.numel(), ptr(cluster), ptr(patch_num), ptr(ws), nbytes,
-                                   stream_ptr()), "ptc_msc_patch_rank")
+    lib().ptc_msc_patch_rank(ptr(c1), ptr(o1), n1, ptr(c2), ptr(o2), n2, o1.numel(), ptr(cluster), ptr(patch_num), ptr(ws), nbytes,
+                             stream_ptr())
     return cluster, patch_num
 
 
@@ -1864,7 +1840,7 @@ def msc_patch_masks(cluster: torch.Tensor, patch_mask: torch.Tensor, n1: int):
         raise PtcoreError("msc_patch_masks: n1 exceeds the number of points")
     m1 = torch.empty(int(n1), dtype=torch.uint8, device=cl.device)
     m2 = torch.empty(n2, dtype=torch.uint8, device=cl.device)
-    check(lib().ptc_msc_patch_masks(ptr(cl), ptr(pm), pm.numel(), int(n1), n2, ptr(m1), ptr(m2), stream_ptr()), "ptc_msc_patch_masks")
+    lib().ptc_msc_patch_masks(ptr(cl), ptr(pm), pm.numel(), int(n1), n2, ptr(m1), ptr(m2), stream_ptr())
     return m1.view(torch.bool), m2.view(torch.bool)
 
 
@@ -1910,8 +1886,8 @@ def msc_nce_fwd(feat1, feat2, match_index, nce_t: float):
     out = torch.empty(3, dtype=torch.float32, device=dev)
     nbytes = lib().ptc_msc_nce_workspace_bytes(p, c)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_msc_nce_fwd(ptr(f1), f1.shape[0], ptr(f2), f2.shape[0], ptr(mi), p, c, float(nce_t), ptr(an), ptr(bn), ptr(vec[0]),
-                                ptr(vec[1]), ptr(vec[2]), ptr(out), ptr(ws), nbytes, stream_ptr()), "ptc_msc_nce_fwd")
+    lib().ptc_msc_nce_fwd(ptr(f1), f1.shape[0], ptr(f2), f2.shape[0], ptr(mi), p, c, float(nce_t), ptr(an), ptr(bn), ptr(vec[0]),
+                          ptr(vec[1]), ptr(vec[2]), ptr(out), ptr(ws), nbytes, stream_ptr())
     return out, (an, bn, vec, mi)
 
 
@@ -1925,8 +1901,8 @@ def msc_nce_bwd(state, n1: int, n2: int, nce_t: float, dloss: torch.Tensor):
     g = dloss.to(torch.float32).reshape(1).contiguous()
     nbytes = lib().ptc_msc_nce_workspace_bytes(p, c)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_msc_nce_bwd(ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(mi), p, c, int(n1), int(n2), float(nce_t),
-                                ptr(g), ptr(d1), ptr(d2), ptr(ws), nbytes, stream_ptr()), "ptc_msc_nce_bwd")
+    lib().ptc_msc_nce_bwd(ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(mi), p, c, int(n1), int(n2), float(nce_t),
+                          ptr(g), ptr(d1), ptr(d2), ptr(ws), nbytes, stream_ptr())
     return d1, d2
 
 
@@ -1967,10 +1943,9 @@ def msc_csc_nce_fwd(feat1, coord1, offset1, feat2, coord2, match_index, nce_t: f
     out = torch.empty(3, dtype=torch.float32, device=dev)
     nbytes = lib().ptc_msc_csc_nce_workspace_bytes(p, c, nb)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_msc_csc_nce_fwd(ptr(f1), f1.shape[0], ptr(f2), f2.shape[0], ptr(x1), ptr(x2), ptr(off), nb, ptr(mi), p, c, float(nce_t),
-                                    float(r1), float(r2), int(partitions), ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(xs[0]), ptr(xs[1]),
-                                    ptr(smi), ptr(start), ptr(lse[0]), ptr(lse[1]), ptr(lse[2]), ptr(vec[2]), ptr(counts), ptr(out), ptr(ws), nbytes, stream_ptr()),
-          "ptc_msc_csc_nce_fwd")
+    lib().ptc_msc_csc_nce_fwd(ptr(f1), f1.shape[0], ptr(f2), f2.shape[0], ptr(x1), ptr(x2), ptr(off), nb, ptr(mi), p, c, float(nce_t),
+                              float(r1), float(r2), int(partitions), ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(xs[0]), ptr(xs[1]),
+                              ptr(smi), ptr(start), ptr(lse[0]), ptr(lse[1]), ptr(lse[2]), ptr(vec[2]), ptr(counts), ptr(out), ptr(ws), nbytes, stream_ptr())
     return out, counts, (an, bn, vec, xs, smi, start, lse)
 
 
@@ -1986,9 +1961,9 @@ def msc_csc_nce_bwd(state, n1: int, n2: int, nce_t: float, r1: float, r2: float,
     g = dloss.to(torch.float32).reshape(1).contiguous()
     nbytes = lib().ptc_msc_csc_nce_workspace_bytes(p, c, nb)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_msc_csc_nce_bwd(ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(xs[0]), ptr(xs[1]), ptr(smi), ptr(start), ptr(lse[1]),
-                                    ptr(lse[2]), ptr(vec[2]), p, c, nb, int(n1), int(n2), float(nce_t), float(r1), float(r2), ptr(g), ptr(d1), ptr(d2),
-                                    ptr(ws), nbytes, stream_ptr()), "ptc_msc_csc_nce_bwd")
+    lib().ptc_msc_csc_nce_bwd(ptr(an), ptr(bn), ptr(vec[0]), ptr(vec[1]), ptr(xs[0]), ptr(xs[1]), ptr(smi), ptr(start), ptr(lse[1]),
+                              ptr(lse[2]), ptr(vec[2]), p, c, nb, int(n1), int(n2), float(nce_t), float(r1), float(r2), ptr(g), ptr(d1), ptr(d2),
+                              ptr(ws), nbytes, stream_ptr())
     return d1, d2
 
 
@@ -2037,8 +2012,8 @@ def cac_pool_fwd(x, logits=None, target=None, offset=None, num_classes=None, con
     passed = torch.empty(s, dtype=torch.int64, device=dev)
     nbytes = lib().ptc_cac_pool_workspace_bytes(n, s, k, c)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_cac_pool_fwd(ptr(x), ptr(logits), ptr(target), ptr(off), n, s, k, c, float(conf_thresh), float(eps), ptr(proto), ptr(wsum),
-                                 ptr(count), ptr(passed), ptr(ws), nbytes, stream_ptr()), "ptc_cac_pool_fwd")
+    lib().ptc_cac_pool_fwd(ptr(x), ptr(logits), ptr(target), ptr(off), n, s, k, c, float(conf_thresh), float(eps), ptr(proto), ptr(wsum),
+                           ptr(count), ptr(passed), ptr(ws), nbytes, stream_ptr())
     return proto, wsum, count, passed
 
 
@@ -2053,8 +2028,8 @@ def cac_pool_bwd(x, logits, target, offset, conf_thresh: float, eps: float, prot
         logits = _cac_rows(logits, "cac_pool_bwd")
     dl = torch.empty_like(logits) if (need_dlogits and logits is not None) else None
     dp = dproto.to(torch.float32).contiguous()          # kept in a name: the copy must outlive the call
-    check(lib().ptc_cac_pool_bwd(ptr(x), ptr(logits), ptr(target), ptr(off), n, s, k, c, float(conf_thresh), float(eps), ptr(proto), ptr(wsum),
-                                 ptr(dp), ptr(dx), ptr(dl), stream_ptr()), "ptc_cac_pool_bwd")
+    lib().ptc_cac_pool_bwd(ptr(x), ptr(logits), ptr(target), ptr(off), n, s, k, c, float(conf_thresh), float(eps), ptr(proto), ptr(wsum),
+                           ptr(dp), ptr(dx), ptr(dl), stream_ptr())
     return dx, dl
 
 
@@ -2069,7 +2044,7 @@ def cac_cos_fwd(x, proto, offset, cos_temp: float):
     out = torch.empty((n, k), dtype=torch.float32, device=x.device)
     nbytes = lib().ptc_cac_cos_workspace_bytes(n, s, k, c)
     ws = _ws(nbytes, x.device)
-    check(lib().ptc_cac_cos_fwd(ptr(x), ptr(p), ptr(off), n, s, k, c, float(cos_temp), ptr(out), ptr(ws), nbytes, stream_ptr()), "ptc_cac_cos_fwd")
+    lib().ptc_cac_cos_fwd(ptr(x), ptr(p), ptr(off), n, s, k, c, float(cos_temp), ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -2083,8 +2058,8 @@ def cac_cos_bwd(x, proto, offset, cos_temp: float, dout):
     nbytes = lib().ptc_cac_cos_workspace_bytes(n, s, k, c)
     ws = _ws(nbytes, x.device)
     do = dout.to(torch.float32).contiguous()            # kept in a name: the copy must outlive the call
-    check(lib().ptc_cac_cos_bwd(ptr(x), ptr(p), ptr(off), n, s, k, c, float(cos_temp), ptr(do), ptr(dx), ptr(dp), ptr(ws), nbytes,
-                                stream_ptr()), "ptc_cac_cos_bwd")
+    lib().ptc_cac_cos_bwd(ptr(x), ptr(p), ptr(off), n, s, k, c, float(cos_temp), ptr(do), ptr(dx), ptr(dp), ptr(ws), nbytes,
+                          stream_ptr())
     return dx, dp
 
 
@@ -2100,8 +2075,8 @@ def cac_distill_fwd(pred, soft, target, smoothness: float, eps: float):
     stats = torch.empty((3, k), dtype=torch.float32, device=pred.device)
     nbytes = lib().ptc_cac_distill_workspace_bytes(n, k)
     ws = _ws(nbytes, pred.device)
-    check(lib().ptc_cac_distill_fwd(ptr(pred), ptr(soft), ptr(tg), n, k, float(smoothness), float(eps), ptr(loss), ptr(stats), ptr(ws), nbytes,
-                                    stream_ptr()), "ptc_cac_distill_fwd")
+    lib().ptc_cac_distill_fwd(ptr(pred), ptr(soft), ptr(tg), n, k, float(smoothness), float(eps), ptr(loss), ptr(stats), ptr(ws), nbytes,
+                              stream_ptr())
     return loss, stats, (pred, soft, tg)
 
 
@@ -2110,8 +2085,8 @@ def cac_distill_bwd(state, smoothness: float, eps: float, stats, dloss):
     n, k = pred.shape
     dpred = torch.empty_like(pred)
     g = dloss.to(torch.float32).reshape(1).contiguous()
-    check(lib().ptc_cac_distill_bwd(ptr(pred), ptr(soft), ptr(tg), n, k, float(smoothness), float(eps), ptr(stats), ptr(g), ptr(dpred),
-                                    stream_ptr()), "ptc_cac_distill_bwd")
+    lib().ptc_cac_distill_bwd(ptr(pred), ptr(soft), ptr(tg), n, k, float(smoothness), float(eps), ptr(stats), ptr(g), ptr(dpred),
+                              stream_ptr())
     return dpred
 
 
@@ -2121,8 +2096,7 @@ def cac_distill_bwd(state, smoothness: float, eps: float, stats, dloss):
 def ppt_head_supported(c: int, d: int, k: int, dtype: torch.dtype) -> bool:
     if dtype not in (torch.float32, torch.bfloat16, torch.float16):
         return False
-    code = {torch.float32: _lib.PTC_F32, torch.float16: _lib.PTC_F16, torch.bfloat16: _lib.PTC_BF16}[dtype]
-    return bool(lib().ptc_ppt_head_supported(int(c), int(d), int(k), code))
+    return bool(lib().ptc_ppt_head_supported(int(c), int(d), int(k), _DT[dtype]))
 
 
 def _ppt_f32(t: torch.Tensor, shape, what: str, dtype=torch.float32) -> torch.Tensor:
@@ -2143,8 +2117,8 @@ def ppt_head_fwd(x, w, b, e, scale: float, eps: float):
     b, e = _ppt_f32(b, (d,), "ppt_head_fwd: b"), _ppt_f32(e, (k, d), "ppt_head_fwd: e")
     logits = torch.empty((n, k), dtype=torch.float32, device=x.device)
     inv = torch.empty(n, dtype=torch.float32, device=x.device)
-    check(lib().ptc_ppt_head_fwd(ptr(x), ptr(w), ptr(b), ptr(e), n, c, d, k, dtype_code(x), float(scale), float(eps), ptr(logits), ptr(inv),
-                                 stream_ptr()), "ptc_ppt_head_fwd")
+    lib().ptc_ppt_head_fwd(ptr(x), ptr(w), ptr(b), ptr(e), n, c, d, k, dtype_code(x), float(scale), float(eps), ptr(logits), ptr(inv),
+                           stream_ptr())
     return logits, inv
 
 
@@ -2165,8 +2139,8 @@ def ppt_head_bwd(x, dlogits, logits, inv_norm, G, M, u, d: int, scale: float, ep
     v, asum, rsum = (torch.empty(s, dtype=torch.float32, device=dev) for s in (c, k, 1))
     nbytes = lib().ptc_ppt_head_workspace_bytes(n, c, int(d), k)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_ppt_head_bwd(ptr(x), ptr(dl), ptr(lg), ptr(iv), ptr(G), ptr(M), ptr(u), n, c, int(d), k, dtype_code(x), float(scale), float(eps),
-                                 ptr(dx), ptr(A), ptr(Bm), ptr(v), ptr(asum), ptr(rsum), ptr(ws), nbytes, stream_ptr()), "ptc_ppt_head_bwd")
+    lib().ptc_ppt_head_bwd(ptr(x), ptr(dl), ptr(lg), ptr(iv), ptr(G), ptr(M), ptr(u), n, c, int(d), k, dtype_code(x), float(scale), float(eps),
+                           ptr(dx), ptr(A), ptr(Bm), ptr(v), ptr(asum), ptr(rsum), ptr(ws), nbytes, stream_ptr())
     return dx, A, Bm, v, asum, rsum
 
 
@@ -2215,8 +2189,8 @@ def sgi_attn_fwd(q, k, v, cu_q, cu_k, mask=None, mask_row_off=None, scale=None):
     scale = float(d) ** -0.5 if scale is None else float(scale)
     out = torch.empty_like(q)
     lse = torch.empty((tq, h), dtype=torch.float32, device=q.device)
-    check(lib().ptc_sgi_attn_fwd(ptr(q), ptr(k), ptr(v), dtype_code(q), ptr(cu_q), ptr(cu_k), s, tq, tk, h, d, ptr(mask), ptr(mask_row_off), scale,
-                                 ptr(out), ptr(lse), stream_ptr()), "ptc_sgi_attn_fwd")
+    lib().ptc_sgi_attn_fwd(ptr(q), ptr(k), ptr(v), dtype_code(q), ptr(cu_q), ptr(cu_k), s, tq, tk, h, d, ptr(mask), ptr(mask_row_off), scale,
+                           ptr(out), ptr(lse), stream_ptr())
     return out, lse
 
 
@@ -2232,8 +2206,8 @@ def sgi_attn_bwd(q, k, v, out, dout, lse, cu_q, cu_k, mask=None, mask_row_off=No
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     nbytes = lib().ptc_sgi_attn_workspace_bytes(tq, h)
     ws = _ws(nbytes, q.device)
-    check(lib().ptc_sgi_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), dtype_code(q), ptr(cu_q), ptr(cu_k), s, tq, tk, h, d, ptr(mask),
-                                 ptr(mask_row_off), scale, ptr(dq), ptr(dk), ptr(dv), ptr(ws), nbytes, stream_ptr()), "ptc_sgi_attn_bwd")
+    lib().ptc_sgi_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), dtype_code(q), ptr(cu_q), ptr(cu_k), s, tq, tk, h, d, ptr(mask),
+                           ptr(mask_row_off), scale, ptr(dq), ptr(dk), ptr(dv), ptr(ws), nbytes, stream_ptr())
     return dq, dk, dv
 
 
@@ -2251,8 +2225,7 @@ def sgi_pack_mask(logits: torch.Tensor, lq: Sequence[int], lk: Sequence[int]):
     row_off, nwords = sgi_offsets(lq, lk, dev, True)
     words = torch.empty(nwords, dtype=torch.int32, device=dev)
     cu_q, cu_k = sgi_cu(lq, dev), sgi_cu(lk, dev)
-    check(lib().ptc_sgi_pack_mask(ptr(x), ptr(logit_off), ptr(cu_q), ptr(cu_k), len(lq), int(sum(lq)), ptr(row_off), ptr(words), stream_ptr()),
-          "ptc_sgi_pack_mask")
+    lib().ptc_sgi_pack_mask(ptr(x), ptr(logit_off), ptr(cu_q), ptr(cu_k), len(lq), int(sum(lq)), ptr(row_off), ptr(words), stream_ptr())
     return words, row_off
 
 
@@ -2272,9 +2245,9 @@ def sgi_match_cost(logits: torch.Tensor, cls: torch.Tensor, lq: Sequence[int], l
     cu_q, cu_k, cu_g = sgi_cu(lq, dev), sgi_cu(lk, dev), sgi_cu(g, dev)
     gc = gt_cls.to(torch.int64).contiguous()
     if ncost:
-        check(lib().ptc_sgi_match_cost(ptr(x), ptr(logit_off), ptr(c), c.shape[1], ptr(cu_q), ptr(cu_k), ptr(cu_g), len(lq), int(sum(lq)),
-                                       ptr(gt_words), ptr(gt_word_off), ptr(gc), ptr(cost_off), float(weights[0]), float(weights[1]),
-                                       float(weights[2]), ptr(cost), stream_ptr()), "ptc_sgi_match_cost")
+        lib().ptc_sgi_match_cost(ptr(x), ptr(logit_off), ptr(c), c.shape[1], ptr(cu_q), ptr(cu_k), ptr(cu_g), len(lq), int(sum(lq)),
+                                 ptr(gt_words), ptr(gt_word_off), ptr(gc), ptr(cost_off), float(weights[0]), float(weights[1]),
+                                 float(weights[2]), ptr(cost), stream_ptr())
     off, host = 0, [0]
     for a, b in zip(lq, g):
         off += int(a) * int(b)
@@ -2302,8 +2275,8 @@ def sgi_targets(instance, segment, sp_inverse, offset, lk: Sequence[int], g: Seq
     counts = torch.empty(ncnt, dtype=torch.int32, device=dev)
     words = torch.empty(nwords, dtype=torch.int32, device=dev)
     inst_cls = torch.empty(ninst, dtype=torch.int64, device=dev)
-    check(lib().ptc_sgi_targets(ptr(inst), ptr(seg), ptr(spi), ptr(off), s, n, ptr(cu_k), ptr(cu_g), ptr(cnt_off), ptr(word_off), nsp, ninst, ncnt,
-                                nwords, ptr(sp_size), ptr(counts), ptr(words), ptr(inst_cls), stream_ptr()), "ptc_sgi_targets")
+    lib().ptc_sgi_targets(ptr(inst), ptr(seg), ptr(spi), ptr(off), s, n, ptr(cu_k), ptr(cu_g), ptr(cnt_off), ptr(word_off), nsp, ninst, ncnt,
+                          nwords, ptr(sp_size), ptr(counts), ptr(words), ptr(inst_cls), stream_ptr())
     return sp_size, counts, words, word_off, inst_cls
 
 
@@ -2352,8 +2325,8 @@ def sonata_colsum(teacher_sim, match_index, temp: float, b=None, max_groups: int
         return r
     bb = None if b is None else _sonata_vec(b, m, "sonata_colsum")
     part = _sonata_partials(m, k, max_groups, t.device)
-    check(lib().ptc_sonata_colsum(ptr(t), dtype_code(t), t.shape[0], ptr(mi), m, k, float(temp), ptr(bb), int(max_groups), ptr(part), ptr(r),
-                                  stream_ptr()), "ptc_sonata_colsum")
+    lib().ptc_sonata_colsum(ptr(t), dtype_code(t), t.shape[0], ptr(mi), m, k, float(temp), ptr(bb), int(max_groups), ptr(part), ptr(r),
+                            stream_ptr())
     return r
 
 
@@ -2369,8 +2342,8 @@ def sonata_rowpass(teacher_sim, match_index, temp: float, a, n: float, want_cols
     if m == 0:
         return c, b, r
     part = _sonata_partials(m, k, max_groups, t.device) if want_colsum else None
-    check(lib().ptc_sonata_rowpass(ptr(t), dtype_code(t), t.shape[0], ptr(mi), m, k, float(temp), ptr(av), float(n), ptr(c), ptr(b),
-                                   int(max_groups), ptr(part), ptr(r), stream_ptr()), "ptc_sonata_rowpass")
+    lib().ptc_sonata_rowpass(ptr(t), dtype_code(t), t.shape[0], ptr(mi), m, k, float(temp), ptr(av), float(n), ptr(c), ptr(b),
+                             int(max_groups), ptr(part), ptr(r), stream_ptr())
     return c, b, r
 
 
@@ -2391,9 +2364,9 @@ def sonata_distill_fwd(teacher_sim, student_sim, match_index, student_batch, num
     vec = torch.zeros((4, m), dtype=torch.float32, device=dev)          # c, lse, row loss, row weight
     scene_mean = torch.zeros(int(num_scenes), dtype=torch.float32, device=dev)
     loss = torch.zeros(1, dtype=torch.float32, device=dev)
-    check(lib().ptc_sonata_distill_fwd(ptr(t), dtype_code(t), t.shape[0], ptr(s), dtype_code(s), s.shape[0], ptr(mi), ptr(sb), int(num_scenes), m,
-                                       k, float(temp), float(student_temp), ptr(av), int(max_groups), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
-                                       ptr(vec[3]), ptr(scene_mean), ptr(loss), stream_ptr()), "ptc_sonata_distill_fwd")
+    lib().ptc_sonata_distill_fwd(ptr(t), dtype_code(t), t.shape[0], ptr(s), dtype_code(s), s.shape[0], ptr(mi), ptr(sb), int(num_scenes), m,
+                                 k, float(temp), float(student_temp), ptr(av), int(max_groups), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]),
+                                 ptr(vec[3]), ptr(scene_mean), ptr(loss), stream_ptr())
     return loss, scene_mean, (t, s, mi, av, vec)
 
 
@@ -2402,9 +2375,9 @@ def sonata_distill_bwd(state, temp: float, student_temp: float, dloss, max_group
     t, s, mi, av, vec = state
     dpred = torch.zeros_like(s)
     g = dloss.detach().to(torch.float32).reshape(1).contiguous()
-    check(lib().ptc_sonata_distill_bwd(ptr(t), dtype_code(t), t.shape[0], ptr(s), dtype_code(s), s.shape[0], ptr(mi), mi.shape[0], t.shape[1],
-                                       float(temp), float(student_temp), ptr(av), ptr(vec[0]), ptr(vec[1]), ptr(vec[3]), ptr(g),
-                                       int(max_groups), ptr(dpred), stream_ptr()), "ptc_sonata_distill_bwd")
+    lib().ptc_sonata_distill_bwd(ptr(t), dtype_code(t), t.shape[0], ptr(s), dtype_code(s), s.shape[0], ptr(mi), mi.shape[0], t.shape[1],
+                                 float(temp), float(student_temp), ptr(av), ptr(vec[0]), ptr(vec[1]), ptr(vec[3]), ptr(g),
+                                 int(max_groups), ptr(dpred), stream_ptr())
     return dpred
 
 
@@ -2425,7 +2398,7 @@ def sonata_patch_rank(grid_coord: torch.Tensor, batch: torch.Tensor, n_batch: in
     ncl = torch.empty(1, dtype=torch.int64, device=key.device)
     nbytes = lib().ptc_pool_maps_workspace_bytes(n)
     ws = _ws(nbytes, key.device)
-    check(lib().ptc_pool_maps_count(ptr(key), ptr(order0), n, 0, ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr()), "ptc_pool_maps_count")
+    lib().ptc_pool_maps_count(ptr(key), ptr(order0), n, 0, ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr())
     bad = ((gl.amax() >> cb) != 0) | (gl.amin() < 0) if n else ncl.new_zeros(())
     return cluster, torch.stack([ncl[0], bad.to(torch.int64)])
 
@@ -2454,8 +2427,7 @@ def concerto_pool_corr(corr: torch.Tensor, perm: Optional[torch.Tensor], idx_ptr
     perm = None if perm is None else perm.to(torch.int64).contiguous()
     if perm is not None and perm.numel() < n:
         raise PtcoreError("concerto_pool_corr: perm is shorter than the points")
-    check(lib().ptc_concerto_pool_corr(ptr(corr), _CONCERTO_CORR_TYPES[corr.dtype], n, v, ptr(perm), ptr(idx_ptr), m, ptr(out), stream_ptr()),
-          "ptc_concerto_pool_corr")
+    lib().ptc_concerto_pool_corr(ptr(corr), _CONCERTO_CORR_TYPES[corr.dtype], n, v, ptr(perm), ptr(idx_ptr), m, ptr(out), stream_ptr())
     return out
 
 
@@ -2501,22 +2473,22 @@ def concerto_patch_pairs(corr: torch.Tensor, scene: torch.Tensor, img_offset: to
         return ConcertoPairs(empty, torch.zeros(1, dtype=torch.int64, device=dev), empty, torch.full((ns, v), -1, dtype=torch.int64, device=dev), rows)
     sentinel = max(int(total_images), 0) * int(patch_h) * int(patch_w)
     keys = torch.empty(e, dtype=torch.int64, device=dev)
-    check(lib().ptc_concerto_pair_keys(ptr(corr.contiguous()), n, ptr(rows), ptr(scene.to(torch.int64).contiguous()),
-                                       ptr(img_offset.to(torch.int64).contiguous()), ptr(img_num.to(torch.int64).contiguous()), ns,
-                                       img_num.numel(), v, int(patch_h), int(patch_w), sentinel, ptr(keys), stream_ptr()), "ptc_concerto_pair_keys")
+    lib().ptc_concerto_pair_keys(ptr(corr.contiguous()), n, ptr(rows), ptr(scene.to(torch.int64).contiguous()),
+                                 ptr(img_offset.to(torch.int64).contiguous()), ptr(img_num.to(torch.int64).contiguous()), ns,
+                                 img_num.numel(), v, int(patch_h), int(patch_w), sentinel, ptr(keys), stream_ptr())
     order, _ = sort_keys(keys[None].contiguous(), 0, max(1, sentinel.bit_length()), want_inverse=False)
     order0 = order[0].contiguous()
     cluster = torch.empty(e, dtype=torch.int64, device=dev)
     ncl = torch.empty(1, dtype=torch.int64, device=dev)
     nbytes = lib().ptc_pool_maps_workspace_bytes(e)
     ws = _ws(nbytes, dev)
-    check(lib().ptc_pool_maps_count(ptr(keys), ptr(order0), e, 0, ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr()), "ptc_pool_maps_count")
+    lib().ptc_pool_maps_count(ptr(keys), ptr(order0), e, 0, ptr(cluster), ptr(ncl), ptr(ws), nbytes, stream_ptr())
     live = keys != sentinel
     n_cluster, n_pairs = torch.stack([ncl[0], live.sum()]).tolist()
     u = n_cluster - (1 if n_pairs < e else 0)          # the sentinel, where present, is the last run
     idx_ptr = torch.empty(n_cluster + 1, dtype=torch.int64, device=dev)
     head = torch.empty(n_cluster, dtype=torch.int64, device=dev)
-    check(lib().ptc_pool_maps_fill(ptr(order0), ptr(cluster), e, n_cluster, ptr(idx_ptr), ptr(head), stream_ptr()), "ptc_pool_maps_fill")
+    lib().ptc_pool_maps_fill(ptr(order0), ptr(cluster), e, n_cluster, ptr(idx_ptr), ptr(head), stream_ptr())
     point = torch.div(order0[:n_pairs], v, rounding_mode="floor")
     perm = point if rows is None else rows[point]
     pair_patch = torch.where(live, cluster, torch.full_like(cluster, -1)).view(ns, v)
@@ -2532,8 +2504,8 @@ def concerto_patch_mean_bwd(dmean: torch.Tensor, pairs: ConcertoPairs, n_out: in
     ns, v = pairs.pair_patch.shape
     alloc = torch.empty if pairs.rows is None else torch.zeros
     out = alloc((int(n_out), c), dtype=dmean.dtype, device=dmean.device)
-    check(lib().ptc_concerto_patch_mean_bwd(ptr(dmean), dtype_code(dmean), ptr(pairs.pair_patch.contiguous()), ptr(pairs.indptr), ptr(pairs.rows),
-                                            ns, int(n_out), v, c, u, ptr(out), stream_ptr()), "ptc_concerto_patch_mean_bwd")
+    lib().ptc_concerto_patch_mean_bwd(ptr(dmean), dtype_code(dmean), ptr(pairs.pair_patch.contiguous()), ptr(pairs.indptr), ptr(pairs.rows),
+                                      ns, int(n_out), v, c, u, ptr(out), stream_ptr())
     return out
 
 
@@ -2557,6 +2529,6 @@ def concerto_align(feature2d: torch.Tensor, patch_ids: torch.Tensor, y: torch.Te
     row = torch.empty(u, dtype=torch.float32, device=y.device)
     loss = torch.empty(1, dtype=torch.float32, device=y.device)
     dy = torch.empty_like(yy) if want_dy else None
-    check(lib().ptc_concerto_align(ptr(x), dtype_code(x), x.shape[0], ptr(ids), ptr(yy), dtype_code(yy), u, d, int(bool(cos_shift)), float(eps),
-                                   ptr(row), ptr(loss), ptr(dy), stream_ptr()), "ptc_concerto_align")
+    lib().ptc_concerto_align(ptr(x), dtype_code(x), x.shape[0], ptr(ids), ptr(yy), dtype_code(yy), u, d, int(bool(cos_shift)), float(eps),
+                             ptr(row), ptr(loss), ptr(dy), stream_ptr())
     return loss, row, dy

@@ -98,38 +98,32 @@ def library_path() -> str:
 
 
 class _EmuLib:
-    """the emulation library with the ctypes signatures of pointcept_amd._lib; anything it does not export is refused"""
+    """the emulation library bound by pointcept_amd._lib.bind (the header's signatures; checked: statuses raise); anything it does
+    not export is refused"""
 
-    def __init__(self):
+    def __init__(self, checked):
         from pointcept_amd import _lib
+
+        self.__dict__.update(vars(_lib.bind(build(), checked, partial=True)))
+
+    def __getattr__(self, name):      # reached only for what bind() did not find in the library
         from pointcept_amd._lib import PtcoreError
 
-        self._cdll, self._sig, self._err = build(), _lib._SIGNATURES, PtcoreError
-        self._fns = {}
-
-    def __getattr__(self, name):
-        fns = self.__dict__["_fns"]
-        if name not in fns:
-            try:
-                fn = getattr(self._cdll, name)
-            except AttributeError:
-                raise self._err(f"{name}: not part of the host emulation (its kernel file uses LDS / wave intrinsics / MFMA)") from None
-            fn.restype, fn.argtypes = self._sig[name]
-            fns[name] = fn
-        return fns[name]
+        raise PtcoreError(f"{name}: not part of the host emulation (its kernel file uses LDS / wave intrinsics / MFMA)")
 
 
 @contextlib.contextmanager
 def emulated_ops():
+    """ops.* on the emulation library: a checked view behind ops.lib / _lib.lib; yields the raw view (status integers)"""
     from pointcept_amd import _lib, ops
 
-    emu = _EmuLib()
+    views = {True: _EmuLib(True), False: _EmuLib(False)}
     saved = [(ops, "lib", ops.lib), (_lib, "lib", _lib.lib), (ops, "require_cuda", ops.require_cuda), (ops, "stream_ptr", ops.stream_ptr)]
     try:
-        ops.lib = _lib.lib = lambda: emu
+        ops.lib = _lib.lib = lambda checked=True: views[checked]
         ops.require_cuda = lambda *a, **k: None
         ops.stream_ptr = lambda: None
-        yield emu
+        yield views[False]
     finally:
         for mod, name, val in saved:
             setattr(mod, name, val)

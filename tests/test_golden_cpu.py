@@ -277,7 +277,6 @@ def test_product_voxel_keys_and_lovasz_steps_on_the_host():
         n = coord.shape[0]
         gc, mn, key = np.empty((n, 3), np.int64), np.empty(3, np.int64), np.empty(n, np.int64)
         c = np.ascontiguousarray(coord)
-        P.probe_voxel_keys.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         P.probe_voxel_keys(c.ctypes.data, n, grid, gc.ctypes.data, mn.ctypes.data, key.ctypes.data)
         v = voxelize.voxels(coord, grid)
         assert np.array_equal(gc, v["grid_coord"]) and np.array_equal(mn, v["min_coord"]) and np.array_equal(key.view(np.uint64), v["key"])
@@ -287,7 +286,6 @@ def test_product_voxel_keys_and_lovasz_steps_on_the_host():
     for n, p in ((1, 1.0), (7, 0.5), (5000, 0.03), (300, 0.0)):
         fg = (rng.random(n) < p).astype(np.int32)
         step = np.empty(n, np.float64)
-        P.probe_lovasz_steps.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
         P.probe_lovasz_steps(fg.ctypes.data, n, step.ctypes.data)
         want = losses.lovasz_grad(fg.astype(np.float64)) if fg.sum() > 0 else np.zeros(n)
         assert np.allclose(step, want, rtol=1e-9, atol=1e-12), (n, p)
@@ -307,42 +305,108 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in L.ptc_version()
 
 
-def test_ctypes_signatures_match_the_header():
-    """every binding in pointcept_amd/_lib.py has the parameter count, the scalar / pointer kind of each parameter and
-    the return kind that include/ptcore.h declares (an int64 passed where the C side reads an int, or a missing
-    argument, corrupts the call silently on x86-64)."""
+def _header_without_comments():
+    header = open(os.path.join(os.path.dirname(GOLD), "..", "include", "ptcore.h")).read()
+    return re.sub(r"/\*.*?\*/|//[^\n]*", "", header, flags=re.S)
+
+
+def test_derived_signatures_match_a_pinned_sample():
+    """pointcept_amd/_lib.py derives restype / argtypes from include/ptcore.h (an int64 passed where the C side reads an int, or a
+    missing argument, corrupts the call silently on x86-64): one declaration of every kind against the literal the hand-written
+    table held for it, and as many entries as the header has `ptc_name(` declarations."""
     from pointcept_amd import _lib
 
-    header = open(os.path.join(os.path.dirname(GOLD), "..", "include", "ptcore.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    decls = re.findall(r"\b(const char\*|int64_t|size_t|int)\s+(ptc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header)
-    assert len(decls) == len(_lib._SIGNATURES)
+    vp, ci, i64, sz, f32, f64, u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_double,
+                                      ctypes.c_uint64)
+    pinned = {
+        "ptc_version": (ctypes.c_char_p, []),
+        "ptc_last_error": (ctypes.c_char_p, []),
+        "ptc_serialize_encode": (ci, [vp, ci, vp, i64, ci, vp, ci, vp, vp]),
+        "ptc_sort_keys_workspace_bytes": (sz, [i64, ci]),
+        "ptc_hash_table_size": (i64, [i64]),
+        "ptc_ptv3_block_abi": (ci, []),
+        "ptc_ptv3_block_fwd": (ci, [vp, vp, vp, vp, vp, sz, vp]),                    # const void* const*, void* const*
+        "ptc_voxel_keys": (ci, [vp, i64, f64, vp, vp, vp, vp]),
+        "ptc_attn_varlen_dropout_fwd": (ci, [vp, vp, i64, i64, ci, ci, f32, ci, f32, u64, vp, vp, vp]),
+        "ptc_msc_csc_nce_fwd": (ci, [vp, i64, vp, i64, vp, vp, vp, ci, vp, i64, ci, f32, f32, f32, ci] + [vp] * 14 + [vp, sz, vp]),
+    }
+    table = _lib.HEADER.signatures
+    for name, want in pinned.items():
+        assert tuple(table[name][:2]) == want, name
+    assert len(table) == 175 == len(re.findall(r"\bptc_\w+\s*\(", _header_without_comments()))
+    assert _lib.exported_symbols() == sorted(table) and _lib._SIGNATURES == {name: tuple(v[:2]) for name, v in table.items()}
 
-    def kind(ctype):
-        if ctype in (ctypes.c_void_p, ctypes.c_char_p):
-            return "ptr"
-        # (c_size_t and c_uint64 are the same ctypes class on LP64: size_t and uint64_t are one kind here)
-        return {ctypes.c_int: "int", ctypes.c_int64: "i64", ctypes.c_size_t: "size", ctypes.c_float: "f32", ctypes.c_double: "f64"}[ctype]
 
-    def ckind(param):
-        param = param.strip()
-        if "*" in param or param.startswith("ptc_stream_t"):
-            return "ptr"
-        base = param.rsplit(" ", 1)[0].replace("const ", "").strip()
-        return {"int": "int", "int64_t": "i64", "size_t": "size", "float": "f32", "double": "f64", "uint64_t": "size"}[base]
+def test_status_calls_are_told_from_value_calls_by_the_header_rule():
+    """the rule the checked handle rests on (ptcore.h, ERRORS): int + last parameter the stream <=> a status.  An entry point that
+    breaks it -- a status call without a stream would go unchecked -- fails here."""
+    from pointcept_amd import _lib
 
+    decls = re.findall(r"\b(const char\*|int64_t|size_t|int)\s+(ptc_\w+)\s*\(([^)]*)\)\s*;", _header_without_comments())
+    assert len(decls) == len(_lib.HEADER.signatures)
+    n_status = n_value = 0
     for ret, name, params in decls:
-        restype, argtypes = _lib._SIGNATURES[name]
-        plist = [q for q in params.split(",") if q.strip() and q.strip() != "void"]
-        assert len(plist) == len(argtypes), (name, len(plist), len(argtypes))
-        assert [ckind(q) for q in plist] == [kind(a) for a in argtypes], name
-        assert kind(restype) == {"const char*": "ptr", "int64_t": "i64", "size_t": "size", "int": "int"}[ret], name
+        params = [p.strip() for p in params.split(",") if p.strip() not in ("", "void")]
+        is_status = _lib.HEADER.signatures[name][2]
+        if is_status:
+            n_status += 1
+            assert ret == "int" and params[-1].startswith("ptc_stream_t"), name
+        else:
+            assert not any("ptc_stream_t" in p for p in params), name                 # no stream: nothing is enqueued
+            if ret == "int":
+                n_value += 1
+                assert not any("*" in p for p in params), name                         # scalars only: a predicate / a query
+                assert "supported" in name or name in ("ptc_ptv3_block_abi", "ptc_ptv3_block_mlp_fused"), name
+    assert (n_status, n_value) == (119, 14)
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("int ptc_x(long n, ptc_stream_t s);", "long n"),                       # a base type the table does not map
+    ("int ptc_y(struct foo f);", "struct foo f"),                            # a by-value struct
+    ("unsigned ptc_z(int n);", "unsigned ptc_z(int n)"),                     # a return type it does not bind
+    ("int ptc_w(int n);\nint ptc_w(int64_t n);", "int ptc_w(int64_t n)"),    # one name, two declarations
+])
+def test_header_parser_refuses_what_it_does_not_understand(decl, named):
+    from pointcept_amd import _lib
+
+    good = "enum ptc_e { PTC_A = 2, PTC_B };\n#define PTC_N 7\nsize_t ptc_ok(const void* const* p,\n   int64_t n); /* int ptc_c(long n); */\n"
+    h = _lib.parse_header(good)
+    assert h.signatures == {"ptc_ok": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int64], False)}
+    assert h.enums == {"ptc_e": {"PTC_A": 2, "PTC_B": 3}} and h.constants == {"PTC_A": 2, "PTC_B": 3, "PTC_N": 7}
+    with pytest.raises(_lib.PtcoreError, match=re.escape(named)):
+        _lib.parse_header(good + decl)
+
+
+def test_constants_come_from_the_header_with_their_values():
+    from pointcept_amd import _lib
+
+    assert (_lib.PTC_F32, _lib.PTC_F16, _lib.PTC_BF16) == (0, 1, 2)
+    assert _lib.DTYPE_CODES == {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+    assert _lib.REDUCE_CODES == {"sum": 0, "mean": 1, "max": 2, "min": 3}
+    assert _lib.ORDER_CODES == {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
+    assert _lib.HEADER.enums["ptc_status"] == {"PTC_OK": 0, "PTC_EINVAL": -1, "PTC_EUNSUPPORTED": -2, "PTC_EHIP": -3, "PTC_EWORKSPACE": -4}
+    E = _lib.block_enums()
+    assert len(E) == 110 and all(not k.startswith("PTC_") for k in E)
+    assert {k: E[k] for k in ("ABI", "I_COUNT", "F_COUNT", "P_COUNT", "O_COUNT", "GS_COUNT")} == \
+        {"ABI": 3, "I_COUNT": 11, "F_COUNT": 4, "P_COUNT": 40, "O_COUNT": 18, "GS_COUNT": 31}
+    assert (E["I_ABI"], E["I_DTYPE"], E["P_W_QKV"], E["O_LSE"], E["G_W_FC2"], E["S_DCONV"]) == (0, 6, 22, 8, 18, 30)
+
+
+def test_host_probe_binds_every_probe_function():
+    from pointcept_amd import _lib
+
+    src = open(os.path.join(os.path.dirname(GOLD), "..", "pointcept_amd", "csrc", "host_probe.cpp")).read()
+    assert set(re.findall(r"^\w+ (probe_\w+)\(", src, flags=re.M)) == set(_lib._PROBES) and len(_lib._PROBES) == 8
+    P = _lib.host_probe()
+    for name, (restype, argtypes) in _lib._PROBES.items():
+        assert getattr(P, name).argtypes == argtypes and getattr(P, name).restype is restype, name
 
 
 def test_argument_validation_returns_error_codes():
+    """the raw handle returns the status integers; the checked handle (what ops.* calls) raises them, with the C message"""
     from pointcept_amd import _lib
 
-    L = _lib.lib()
+    L = _lib.lib(checked=False)
     oc = (ctypes.c_int * 1)(0)
     rc = L.ptc_serialize_encode(None, 1, None, 10, 17, ctypes.cast(oc, ctypes.c_void_p), 1, None, None)
     assert rc == -1 and b"depth" in L.ptc_last_error()
@@ -387,6 +451,27 @@ def test_argument_validation_returns_error_codes():
     assert L.ptc_ptv3_block_fwd(iv, fv, pin, pout, None, 0, None) == -4 and b"workspace" in L.ptc_last_error()
     iv[E["I_ABI"]] = 2
     assert L.ptc_ptv3_block_fwd(iv, fv, pin, pout, None, 0, None) == -1 and b"ABI" in L.ptc_last_error()
+    # the same calls on the checked handle: PtcoreError, .code the status, the text check() gives ("<name> failed with code <rc>: <msg>")
+    C = _lib.lib()
+    assert C is not L and C.ptc_serialize_encode is not L.ptc_serialize_encode
+    for name, args, code, word in (
+            ("ptc_serialize_encode", (None, 1, None, 10, 17, ctypes.cast(oc, ctypes.c_void_p), 1, None, None), -1, "depth"),
+            ("ptc_attn_varlen_fwd", (None, None, 1, 10, 2, 4096, 0.25, 2, None, None, None), -2, "max_seqlen"),
+            ("ptc_spconv_fwd", (None, 10, None, None, None, 10, 27, 6, 32, 2, None, None), -2, "c_in")):
+        assert getattr(L, name)(*args) == code
+        want = f"{name} failed with code {code}: " + L.ptc_last_error().decode()
+        with pytest.raises(_lib.PtcoreError) as e:
+            getattr(C, name)(*args)
+        assert e.value.code == code and str(e.value) == want and word in want
+        with pytest.raises(_lib.PtcoreError) as e:
+            _lib.check(getattr(L, name)(*args), name)
+        assert e.value.code == code and str(e.value) == want
+    assert C.ptc_rope3d_xyz(None, 2, None, 2, None, None, 0, 3, 2, 4, 18, 1.0, None) == 0               # PTC_OK passes through
+    # predicates and size queries return their values on both handles and never raise
+    for H in (L, C):
+        assert H.ptc_layer_norm_supported(7) == 0 and H.ptc_layer_norm_supported(64) == 1
+        assert H.ptc_spconv_fwd_blk_workspace_bytes(9000, 27, 128, 96) == need and H.ptc_ptv3_block_abi() == 3
+        assert getattr(H.ptc_layer_norm_supported, "errcheck", None) is None
 
 
 def test_ops_refuse_cpu_tensors():

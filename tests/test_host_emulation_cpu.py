@@ -15,7 +15,6 @@ running LDS counter and the lowest lane of each digit group then publishes the n
 `__builtin_amdgcn_wave_barrier()` -- no instruction, the gfx950 binary is byte-identical (tools/kernel_fingerprint.py) -- which the
 emulator honours as a wave-level wait; the sort and everything built on it runs here since.)
 ptc_rope3d_xyz (written after round 2's GPU time was spent) has only ever run here."""
-import ctypes
 import os
 import shutil
 import subprocess
@@ -35,12 +34,9 @@ def emu():
 
     if not emu_backend.available():
         pytest.skip("no host clang++ under /opt/rocm")
-    L = emu_backend.build()
-    vp, i64, ci, cf = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
-    L.ptc_rope3d.argtypes = [vp, ci, vp, i64, ci, ci, cf, cf, vp]
-    L.ptc_rope3d_xyz.argtypes = [vp, ci, vp, ci, vp, vp, i64, ci, ci, ci, ci, cf, vp]
-    L.ptc_serialize_encode.argtypes = [vp, ci, vp, i64, ci, vp, ci, vp, vp]
-    L.ptc_last_error.restype = ctypes.c_char_p
+    from pointcept_amd import _lib
+
+    L = _lib.bind(emu_backend.build(), checked=False, partial=True)     # the header's signatures; status integers returned
     L.emu_last_error = L.ptc_last_error
     return L
 
@@ -162,6 +158,38 @@ def test_serialize_encode_on_the_host_emulation_is_bit_exact(emu):
     bad = np.asarray([0, 9], dtype=np.int32)
     assert emu.ptc_serialize_encode(None, 1, None, 10, 8, bad.ctypes.data, 2, None, None) == -1 and b"bad order" in emu.emu_last_error()
     assert emu.ptc_serialize_encode(None, 1, None, 0, 8, orders.ctypes.data, 4, None, None) == 0
+
+
+def test_checked_and_raw_views_do_not_share_function_objects(emu):
+    """a checked view bound FIRST on the same CDLL (attribute access on a CDLL caches one function object: an errcheck set through
+    it would act in every view): the raw views -- the fixture's, bound before, and one bound after -- still return the status, the
+    checked one raises it with the library's message"""
+    import emu_backend
+    from pointcept_amd import _lib
+
+    cdll = emu_backend.build()
+    checked = _lib.bind(cdll, checked=True, partial=True)
+    raw = _lib.bind(cdll, checked=False, partial=True)
+    orders = np.asarray([0, 1, 2, 3], dtype=np.int32)
+    bad = (None, 1, None, 10, 17, orders.ctypes.data, 4, None, None)
+    assert checked.ptc_serialize_encode is not raw.ptc_serialize_encode
+    assert raw.ptc_serialize_encode(*bad) == -1 and emu.ptc_serialize_encode(*bad) == -1
+    with pytest.raises(_lib.PtcoreError, match=r"^ptc_serialize_encode failed with code -1: .*depth") as e:
+        checked.ptc_serialize_encode(*bad)
+    assert e.value.code == -1
+    assert raw.ptc_serialize_encode(*bad) == -1 and b"depth" in raw.ptc_last_error()
+    assert checked.ptc_serialize_encode(None, 1, None, 0, 8, orders.ctypes.data, 4, None, None) == 0
+    # emulated_ops(): checked behind ops.lib / _lib.lib, the raw view yielded and behind lib(checked=False)
+    from pointcept_amd import ops
+
+    with emu_backend.emulated_ops() as raw2:
+        assert _lib.lib(checked=False) is raw2 and ops.lib() is _lib.lib() and ops.lib() is not raw2
+        assert raw2.ptc_serialize_encode(*bad) == -1
+        with pytest.raises(_lib.PtcoreError, match="depth"):
+            ops.lib().ptc_serialize_encode(*bad)
+        with pytest.raises(_lib.PtcoreError, match="ptc_no_such_entry: not part of the host emulation"):
+            ops.lib().ptc_no_such_entry
+    assert emu.ptc_serialize_encode(*bad) == -1
 
 
 # ---- the bodies of -m gpu kernel tests on the emulated ops (tests/emu_backend.py) ---------------------------------------------
