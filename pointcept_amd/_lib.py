@@ -1,5 +1,6 @@
 """ctypes binding of libptcore.so, derived from include/ptcore.h (the C-ABI's one definition).
 
+(The ptc_aug_* entry points of csrc/augment.hip are declared in csrc/ptcore_augment.h, which is read the same way.)
 The header is read once, at import: its declarations give every entry point's restype / argtypes and whether it
 returns a status, its enums and integer #defines give the constants (PTC_F32 ..., REDUCE_CODES, ORDER_CODES,
 block_enums()).  Nothing of the header is written out a second time here; the parser raises on a declaration it
@@ -28,6 +29,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libptcore.so")
 PROBE_PATH = os.path.join(HERE, "libptcore_hostprobe.so")
 HEADER_PATH = os.path.normpath(os.path.join(HERE, "..", "include", "ptcore.h"))
+AUGMENT_HEADER_PATH = os.path.join(HERE, "csrc", "ptcore_augment.h")      # the augmentation section of the C-ABI, a header of its own
 
 c_i64, c_int, c_f32, c_size, c_ptr = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 
@@ -95,15 +97,17 @@ def parse_header(text: str) -> Header:
     return Header(signatures, enums, constants)
 
 
-def _read_header():
+def _read_header(path=HEADER_PATH):
     try:
-        raw = open(HEADER_PATH, "rb").read()
+        raw = open(path, "rb").read()
     except OSError as e:
-        raise PtcoreError(f"cannot read {HEADER_PATH} (the C-ABI's definition; this binding is derived from it): {e}") from e
+        raise PtcoreError(f"cannot read {path} (the C-ABI's definition; this binding is derived from it): {e}") from e
     return parse_header(raw.decode()), f"{zlib.crc32(raw) & 0xffffffff:08x}"
 
 
 HEADER, HEADER_CRC = _read_header()
+# csrc/ptcore_augment.h: the ptc_aug_* entry points, bound by bind() beside the header's; HEADER stays include/ptcore.h alone
+AUGMENT_HEADER = _read_header(AUGMENT_HEADER_PATH)[0]
 # name -> (restype, argtypes): the computed table under the name of the literal it replaces.  Nothing in this tree reads it; it is
 # what a binder written against that literal reads (tests/emu_backend.py as it was before bind() existed still works on this package)
 _SIGNATURES = {name: (restype, argtypes) for name, (restype, argtypes, _) in HEADER.signatures.items()}
@@ -133,7 +137,7 @@ def bind(cdll, checked: bool, partial: bool = False):
     view = types.SimpleNamespace()
     last_error = cdll["ptc_last_error"]      # the errchecks' own function object: they depend on no view
     last_error.restype, last_error.argtypes = HEADER.signatures["ptc_last_error"][:2]
-    for name, (restype, argtypes, is_status) in HEADER.signatures.items():
+    for name, (restype, argtypes, is_status) in {**HEADER.signatures, **AUGMENT_HEADER.signatures}.items():
         try:
             fn = cdll[name]
         except AttributeError:   # the library does not export a declared symbol
@@ -182,6 +186,9 @@ def lib(checked: bool = True):
     if got != HEADER_CRC:
         raise PtcoreError(f"{LIB_PATH} was built against another include/ptcore.h (abi {got}, header {HEADER_CRC}): rebuild "
                           "(python -m pointcept_amd.build --force)")
+    if raw.ptc_aug_abi() != AUGMENT_HEADER.constants["PTC_AUG_ABI"]:
+        raise PtcoreError(f"{LIB_PATH} was built against another csrc/ptcore_augment.h (PTC_AUG_ABI {raw.ptc_aug_abi()}, header "
+                          f"{AUGMENT_HEADER.constants['PTC_AUG_ABI']}): rebuild (python -m pointcept_amd.build --force)")
     _views = (raw, bind(cdll, checked=True))      # one assignment: another thread sees neither view or both
     return _views[checked]
 

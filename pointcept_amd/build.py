@@ -60,6 +60,7 @@ HIP_SOURCES = [
     "ppt.hip",
     "concerto.hip",
     "criteria.hip",
+    "augment.hip",
 ]
 CXX_SOURCES = ["core.cpp"]
 PROBE_SOURCES = ["host_probe.cpp"]

@@ -58,6 +58,9 @@ settings), and so a regression can be bisected without a rebuild.
                      CrossEntropyLoss, FocalLoss, DiceLoss; criteria.Criteria) run as their torch twins -- the reference's own
                      expressions, several fp32 [N, C] temporaries per term and direction -- instead of one fused pass per direction
                      (A/B baseline, and the CPU path); the default CrossEntropyLoss and LovaszLoss keep their kernels either way
+  PTC_AUGMENT=0      the device-side point augmentations (augment.py: CenterShift ... ElasticDistortion, the Chromatic* ops, Compose)
+                     run as their torch twins -- the reference's transforms op by op in fp32, one [n, 3] temporary or more per
+                     transform -- instead of the pending-affine / flush kernels of csrc/augment.hip (A/B baseline, and the CPU path)
   PTC_FUSE_BLOCK=0   the three residual joints of a PTv3 Block run as separate LayerNorm / add / cast
                      kernels instead of the fused add_norm passes
 """
@@ -91,6 +94,7 @@ SONATA_KERNELS = _flag("PTC_SONATA", True)
 PPT_KERNELS = _flag("PTC_PPT", True)
 CONCERTO_KERNELS = _flag("PTC_CONCERTO", True)
 CRITERIA_KERNELS = _flag("PTC_CRITERIA", True)
+AUGMENT_KERNELS = _flag("PTC_AUGMENT", True)
 WGRAD_BLK = _flag("PTC_WGRAD_BLK", True)
 FUSE_BN_TAIL = _flag("PTC_FUSE_BN_TAIL", True)
 BATCH_BN_COUNTERS = _flag("PTC_BATCH_BN_COUNTERS", True)

@@ -2532,3 +2532,139 @@ def concerto_align(feature2d: torch.Tensor, patch_ids: torch.Tensor, y: torch.Te
     lib().ptc_concerto_align(ptr(x), dtype_code(x), x.shape[0], ptr(ids), ptr(yy), dtype_code(yy), u, d, int(bool(cos_shift)), float(eps),
                              ptr(row), ptr(loss), ptr(dy), stream_ptr())
     return loss, row, dy
+
+
+# ------------------------------------------------------------------------------------------------
+# device-side point augmentation (csrc/augment.hip)
+# ------------------------------------------------------------------------------------------------
+AUG_CENTER_SHIFT, AUG_ROTATE, AUG_SCALE, AUG_FLIP, AUG_SHIFT = range(5)                 # ptc_aug_compose descriptor kinds
+AUG_C_AUTOCONTRAST, AUG_C_TRANSLATION, AUG_C_JITTER, AUG_C_NORMALIZE = range(4)          # ptc_aug_apply colour op kinds
+AUG_MAX_OPS, AUG_MAX_COLOR_OPS = 16, 8
+AUG_STREAM_JITTER, AUG_STREAM_COLOR, AUG_STREAM_ELASTIC = 0, 1, 2                        # generator streams (elastic stage s: 2 + s)
+
+
+def _aug_points(t: Optional[torch.Tensor], what: str, n: Optional[int] = None) -> Optional[torch.Tensor]:
+    """[n, 3] fp32 contiguous (converted when it is anything else)"""
+    if t is None:
+        return None
+    if t.dim() != 2 or t.shape[1] != 3 or (n is not None and t.shape[0] != n):
+        raise PtcoreError(f"augment: {what} must be [{'n' if n is None else n}, 3], got {tuple(t.shape)}")
+    if t.shape[0] == 0:
+        raise PtcoreError("augment: empty point cloud")
+    return t.to(torch.float32).contiguous()
+
+
+def aug_state(device):
+    """-> (aff [21] float64, stats [12] float64) on `device`, uninitialised: aug_compose(from_identity=True) / aug_reduce fill them"""
+    return torch.empty(21, dtype=torch.float64, device=device), torch.empty(12, dtype=torch.float64, device=device)
+
+
+def aug_reduce(coord: Optional[torch.Tensor], color: Optional[torch.Tensor], aff: Optional[torch.Tensor], stats: torch.Tensor) -> None:
+    """stats[0:6] = min / max of A p + t over coord (aff None: of coord), stats[6:12] = channel min / max of color; a part given as None
+    keeps its half.  One read-only pass and a finish launch; no host read."""
+    require_cuda(coord, color, aff, stats)
+    coord, color = _aug_points(coord, "coord"), _aug_points(color, "color")
+    ref = coord if coord is not None else color
+    if ref is None:
+        raise PtcoreError("aug_reduce: neither coord nor color")
+    n = ref.shape[0]
+    partial = torch.empty((lib().ptc_aug_partials(n), 12), dtype=torch.float64, device=ref.device)
+    lib().ptc_aug_reduce(ptr(coord), ptr(color), n, ptr(aff), ptr(partial), ptr(stats), stream_ptr())
+
+
+def aug_compose(ops_list: Sequence[Sequence[float]], aff: torch.Tensor, stats: Optional[torch.Tensor], from_identity: bool) -> None:
+    """advance the pending affine `aff` by the descriptors (kind, arguments...) in order; the ones that need the bounding box read it
+    from `stats` on the device.  One launch per 16 descriptors; no host read."""
+    require_cuda(aff, stats)
+    ops_list = list(ops_list)
+    if not ops_list and from_identity:
+        ops_list = [(AUG_SHIFT, 0.0, 0.0, 0.0)]
+    for at in range(0, len(ops_list), AUG_MAX_OPS):
+        chunk = ops_list[at:at + AUG_MAX_OPS]
+        flat = (ctypes.c_double * (8 * len(chunk)))()
+        for i, op in enumerate(chunk):
+            if len(op) > 8:
+                raise PtcoreError(f"aug_compose: descriptor {op} has more than 8 entries")
+            for j, v in enumerate(op):
+                flat[i * 8 + j] = float(v)
+        lib().ptc_aug_compose(ctypes.cast(flat, ctypes.c_void_p), len(chunk), int(bool(from_identity and at == 0)), ptr(aff), ptr(stats),
+                              stream_ptr())
+
+
+def aug_apply(coord=None, normal=None, color=None, aff=None, stats=None, jitter=None, clip_range=None, color_ops=(), want_stats=False):
+    """The flush -> (coord', normal', color'), each None when its input is None; every given part is written once, into a new
+    tensor.  jitter = (sigma, clip, noise [n,3] | None, seed); clip_range = six floats; color_ops = rows (kind, p0, p1, p2,
+    noise [n,3] | None, seed, stream).  want_stats: stats[0:6] becomes the box of coord'.  No host read."""
+    require_cuda(coord, normal, color, aff, stats)
+    coord, normal, color = _aug_points(coord, "coord"), _aug_points(normal, "normal"), _aug_points(color, "color")
+    ref = coord if coord is not None else normal if normal is not None else color
+    if ref is None:
+        raise PtcoreError("aug_apply: nothing to write")
+    n, device = ref.shape[0], ref.device
+    color_ops = list(color_ops)
+    if len(color_ops) > AUG_MAX_COLOR_OPS:
+        raise PtcoreError(f"aug_apply: {len(color_ops)} colour ops (at most {AUG_MAX_COLOR_OPS} per flush)")
+    k = len(color_ops)
+    flat = (ctypes.c_double * max(6 * k, 1))()
+    noise_ptrs = (ctypes.c_void_p * max(k, 1))()
+    keep = []
+    for i, (kind, p0, p1, p2, noise, seed, stream) in enumerate(color_ops):
+        noise = _aug_points(noise, "colour noise", n)
+        require_cuda(noise)
+        keep.append(noise)
+        flat[i * 6:i * 6 + 6] = [float(kind), float(p0), float(p1), float(p2), float(int(seed) % (1 << 53)), float(stream)]
+        noise_ptrs[i] = ptr(noise) or None
+    jn = None
+    if jitter is not None:
+        jn = _aug_points(jitter[2], "jitter noise", n)
+        require_cuda(jn)
+    rng = None if clip_range is None else (ctypes.c_double * 6)(*[float(v) for v in clip_range])
+    out_c = None if coord is None else torch.empty_like(coord)
+    out_n = None if normal is None else torch.empty_like(normal)
+    out_k = None if color is None else torch.empty_like(color)
+    partial = torch.empty((lib().ptc_aug_partials(n), 6), dtype=torch.float64, device=device) if want_stats else None
+    lib().ptc_aug_apply(ptr(coord), ptr(normal), ptr(color), n, ptr(aff), ptr(stats), int(jitter is not None),
+                        float(jitter[0]) if jitter else 0.0, float(jitter[1]) if jitter else 1.0, ptr(jn),
+                        int(jitter[3]) % (1 << 63) if jitter else 0, None if rng is None else ctypes.cast(rng, ctypes.c_void_p),
+                        ctypes.cast(flat, ctypes.c_void_p), ctypes.cast(noise_ptrs, ctypes.c_void_p), k, ptr(out_c), ptr(out_n), ptr(out_k),
+                        ptr(partial), ptr(stats) if want_stats else None, stream_ptr())
+    return out_c, out_n, out_k
+
+
+def aug_noise(seed: int, stream: int, count: int, device) -> torch.Tensor:
+    """z [count] fp32: elements 0 .. count-1 of the generator's stream (seed, stream) -- what the kernels evaluate in place"""
+    out = torch.empty(int(count), dtype=torch.float32, device=device)
+    require_cuda(out)
+    lib().ptc_aug_noise(int(seed) % (1 << 63), int(stream), int(count), ptr(out), stream_ptr())
+    return out
+
+
+def aug_elastic_grid(dims, noise: Optional[torch.Tensor], seed: int, stream: int, device) -> torch.Tensor:
+    """-> grid [dx, dy, dz, 3] fp32: standard-normal noise (the given [dx, dy, dz, 3] tensor, or the generator's stream) after the
+    reference's two rounds of width-3 box filters, in one launch"""
+    dx, dy, dz = (int(d) for d in dims)
+    if noise is not None:
+        if tuple(noise.shape) != (dx, dy, dz, 3):
+            raise PtcoreError(f"ElasticDistortion: noise of shape {tuple(noise.shape)} for a grid of {(dx, dy, dz, 3)}")
+        buf = noise.to(device=device, dtype=torch.float32).contiguous()
+    else:
+        buf = torch.empty((dx, dy, dz, 3), dtype=torch.float32, device=device)
+    grid = torch.empty((dx, dy, dz, 3), dtype=torch.float32, device=device)
+    require_cuda(buf, grid)
+    lib().ptc_aug_elastic_grid(ptr(buf), int(noise is None), int(seed) % (1 << 63), int(stream), dx, dy, dz, ptr(grid), stream_ptr())
+    return grid
+
+
+def aug_elastic_apply(coord: torch.Tensor, aff: Optional[torch.Tensor], stats: torch.Tensor, grid: torch.Tensor, granularity: float,
+                      magnitude: float) -> torch.Tensor:
+    """coord' [n,3] = p + trilinear(grid)(p) * magnitude with p = A coord + t; stats[0:3] = the min of p on entry, stats[0:6] = the box of
+    coord' on return.  No host read."""
+    require_cuda(coord, aff, stats, grid)
+    coord = _aug_points(coord, "coord")
+    n = coord.shape[0]
+    dx, dy, dz = grid.shape[:3]
+    out = torch.empty_like(coord)
+    partial = torch.empty((lib().ptc_aug_partials(n), 6), dtype=torch.float64, device=coord.device)
+    lib().ptc_aug_elastic_apply(ptr(coord), n, ptr(aff), ptr(stats), ptr(grid), dx, dy, dz, float(granularity), float(magnitude), ptr(out),
+                                ptr(partial), ptr(stats), stream_ptr())
+    return out
