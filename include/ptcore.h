@@ -55,6 +55,40 @@ enum ptc_order { PTC_ORDER_Z = 0, PTC_ORDER_Z_TRANS = 1, PTC_ORDER_HILBERT = 2, 
  * pointcept/models/point_transformer_v3/point_transformer_v3m1_base.py:416-421 */
 enum ptc_reduce { PTC_REDUCE_SUM = 0, PTC_REDUCE_MEAN = 1, PTC_REDUCE_MAX = 2, PTC_REDUCE_MIN = 3 };
 
+/* ------------------------------------------------------------------------------------------
+ * LIMITS and code sets: the ONE definition of every number that decides whether a call is served.  The kernel sources take their
+ * local names from these (csrc: `#define LV_MAX_C PTC_LOVASZ_DENSE_MAX_C`), the comments below refer to them by name, and a binding
+ * reads them from this header (plain integer literals: pointcept_amd/_lib.py parses them; ops.py derives its attributes from them
+ * without loading the library).  The augmentation limits and kinds are in csrc/ptcore_augment.h.  Shape rules that are more than one
+ * number are entry points (ptc_spconv_blk_min_rows, ptc_attn_rpe_supported, ... -- the *_supported predicates of each section).
+ * ------------------------------------------------------------------------------------------ */
+#define PTC_VOX_BITS 18               /* F: bits per coordinate of the voxel key: coordinates in [0, 2^PTC_VOX_BITS) */
+#define PTC_VOX_BATCH_MAX 1023        /* F: most batch items the voxel key holds */
+#define PTC_BLOCK_BM 128              /* G: rows per block of the block-local tables (ptc_rulebook_blocks) */
+#define PTC_BLOCK_HCAP 416            /* G: halo capacity (rows) of a block that conv7 / wgrad7 stage in LDS */
+#define PTC_ATTN_MAX_SEQLEN 1024      /* H: longest attention window (keys) of any head_dim */
+#define PTC_ATTN_HEAD_DIM 16          /* H: head_dim of the base kernels, their dropout form and the RPE form */
+#define PTC_ATTN_RPE_MAX_POS_BND 4096 /* H: largest pos_bnd of the RPE table */
+#define PTC_CRITERIA_ROWS_MAX_C 32    /* criteria: classes up to which every term is served */
+#define PTC_CRITERIA_CE_MAX_C 1024    /* criteria: classes up to which the cross-entropy term alone is served */
+#define PTC_LOVASZ_DENSE_MAX_C 64     /* I: classes of the dense [c, n] Lovasz path (ptc_lovasz_softmax_*) */
+#define PTC_LOVASZ_MAX_C 1024         /* I: classes of the row-compacted Lovasz path (ptc_lovasz_present_*) */
+#define PTC_PG_MAX_NEIGHBOURS 1000    /* R: a ball-query list is truncated to its first PTC_PG_MAX_NEIGHBOURS entries */
+#define PTC_MSC_MAX_K 8               /* S: most matches per query of ptc_msc_match */
+
+/* `flags` of the ptc_criteria_* calls: the terms, OR-ed */
+enum ptc_criteria_term { PTC_CRITERIA_CE = 1, PTC_CRITERIA_FOCAL = 2, PTC_CRITERIA_DICE = 4 };
+/* `act` of the ptc_batch_norm_*act* calls (section J) */
+enum ptc_act { PTC_ACT_NONE = 0, PTC_ACT_GELU = 1, PTC_ACT_RELU = 2 };
+/* `ctype` of ptc_concerto_pool_corr: the element type of the correspondence tensor */
+enum ptc_corr_type { PTC_CORR_F32 = 0, PTC_CORR_I32 = 1, PTC_CORR_I64 = 2 };
+/* `mode` of ptc_edge_rows_fwd, of ptc_edge_reduce_fwd and of ptc_edge_scatter_bwd (the formulas are stated with the calls) */
+enum ptc_edge_rows { PTC_EDGE_ROWS_GROUP = 0, PTC_EDGE_ROWS_SUB = 1, PTC_EDGE_ROWS_REL = 2 };
+enum ptc_edge_reduce { PTC_EDGE_REDUCE_INTERP = 0, PTC_EDGE_REDUCE_AGG = 1, PTC_EDGE_REDUCE_POS = 2 };
+enum ptc_edge_scatter { PTC_EDGE_SCATTER_GROUP = 0, PTC_EDGE_SCATTER_SUB = 1, PTC_EDGE_SCATTER_INTERP = 2, PTC_EDGE_SCATTER_AGG = 3 };
+/* the consumers of the block-local tables that ptc_spconv_blk_min_rows answers for */
+enum ptc_blk_consumer { PTC_CONSUMER_CONV7 = 0, PTC_CONSUMER_CONV8 = 1, PTC_CONSUMER_WGRAD7 = 2 };
+
 const char* ptc_version(void);
 const char* ptc_last_error(void);
 
@@ -174,7 +208,9 @@ int ptc_pool_level_counts(const int64_t* code0, const int64_t* order0, int64_t n
 int ptc_gather_rows(const void* src, int64_t n_src, const int64_t* idx, const int64_t* idx2,
                     int64_t n_out, int c, int dtype, void* out, ptc_stream_t stream);
 /* out[i] = addend[i] + src[idx[i]] (idx[i] < 0: addend[i]) in one pass, one rounding in the feature dtype -- SerializedUnpooling's
- * `parent.feat + point.feat[inverse]` (pointcept/models/point_transformer_v3/point_transformer_v3m1_base.py:478).  c a multiple of a 16-byte lane. */
+ * `parent.feat + point.feat[inverse]` (pointcept/models/point_transformer_v3/point_transformer_v3m1_base.py:478).  c a multiple of a 16-byte lane:
+ * ptc_gather_rows_add_supported(c, dtype) is the rule the call checks (1 / 0). */
+int ptc_gather_rows_add_supported(int c, int dtype);
 int ptc_gather_rows_add(const void* src, int64_t n_src, const int64_t* idx, const void* addend, int64_t n_out, int c, int dtype,
                         void* out, ptc_stream_t stream);
 int ptc_segment_csr_fwd(const void* src, const int64_t* perm, const int64_t* indptr, int64_t n_seg,
@@ -244,7 +280,7 @@ int ptc_spconv_fwd(const void* in, int64_t n_in, const void* weight, const float
 /* Block-local form of a submanifold 3^3 gather table (csrc/blocks.hip) and the convolution that uses it (csrc/conv7.h).
  * Replaces nothing new in the reference: it is a faster way to run the SAME SubMConv3d call sites as ptc_spconv_fwd
  * (ptv3m1:278-284; spconv_unet_v1m1_base.py:49-68) when rows are in a spatial (curve) order.
- *   ptc_rulebook_blocks: for every block of bm = 128 consecutive output rows of nbr [27][n]
+ *   ptc_rulebook_blocks: for every block of bm = PTC_BLOCK_BM consecutive output rows of nbr [27][n]
  *       hid  [n_blocks][hcap] int32 = the distinct input rows named by nbr[:, block], ascending, padded with the last one to
  *                                     a multiple of 16 entries
  *       hcnt [n_blocks]       int32 = how many (-1 = more than hcap: block served through the global table)
@@ -262,9 +298,10 @@ int ptc_spconv_fwd(const void* in, int64_t n_in, const void* weight, const float
  *     hcap a multiple of 16, < 512.
  *   ptc_spconv_fwd_blk: same result as ptc_spconv_fwd(in, ..., nbr, ...) up to the fp32 rounding of a different summation
  *       order, with the input rows of a block staged once in LDS and the weights held in registers.  16-bit dtypes,
- *       kv = 27, bm = 128, n_in = n_out, and either c_in = c_out in {32, 64}, hcap = 416, n_out >= 4096 (csrc/conv7.h) or c_in a
- *       multiple of 32 in [96, 1024], c_out a multiple of 32 up to 1024, 16 <= hcap <= 511, n_out >= 256 (csrc/conv8.h, round 6;
- *       PTC_CONV8=0 in the environment turns it off); any other shape is forwarded to ptc_spconv_fwd.  The wide form rewrites the
+ *       kv = 27, bm = PTC_BLOCK_BM, n_in = n_out, and either c_in = c_out in {32, 64}, hcap = PTC_BLOCK_HCAP (conv7_supported, csrc/conv7.h) or
+ *       c_in a multiple of 32 in [96, 1024], c_out a multiple of 32 up to 1024, 16 <= hcap <= 511 (conv8_supported, csrc/conv8.h, round 6;
+ *       PTC_CONV8=0 in the environment turns it off), each from its own row count up -- ptc_spconv_blk_min_rows states both rules for a
+ *       caller; any other shape is forwarded to ptc_spconv_fwd.  The wide form rewrites the
  *       weights into MFMA fragment order in `workspace` on every call: workspace >= ptc_spconv_fwd_blk_workspace_bytes
  *       (c_out * 27 * c_in * 2 bytes rounded up to 256 in the wide channel range, else 0; a function of kv and the channel counts
  *       alone, n_out is ignored), 16-byte aligned -- PTC_EWORKSPACE when it is NULL or too small; the other forms ignore it.
@@ -283,6 +320,12 @@ int ptc_spconv_fwd_blk(const void* in, int64_t n_in, const void* weight, const f
                        int kv, int c_in, int c_out, int dtype, void* out, void* workspace, size_t workspace_bytes,
                        ptc_stream_t stream);
 size_t ptc_spconv_fwd_blk_workspace_bytes(int64_t n_out, int kv, int c_in, int c_out);
+/* The plan of the block-local tables for one layer shape, from the predicates the launch paths themselves use (conv7_supported,
+ * conv8_supported with PTC_CONV8, wgrad7_supported): the smallest n_out from which `consumer` (enum ptc_blk_consumer: the convolution
+ * kernels conv7 / conv8 behind ptc_spconv_fwd_blk, the weight gradient wgrad7 behind ptc_spconv_wgrad_blk) takes tables built with
+ * bm = PTC_BLOCK_BM, hcap = PTC_BLOCK_HCAP for (kv, c_in, c_out, dtype), or -1 when it never does (the call is then forwarded to the
+ * global-gather kernels and the tables would go unused).  A function of the shape alone: a caller caches it per shape and compares rows. */
+int64_t ptc_spconv_blk_min_rows(int consumer, int kv, int c_in, int c_out, int dtype);
 size_t ptc_spconv_wgrad_blk_workspace_bytes(int64_t n_out, int kv, int c_in, int c_out);
 int ptc_spconv_wgrad_blk(const void* in, int64_t n_in, const void* dout, const int32_t* nbr, const void* tab, const int32_t* hid,
                          const int32_t* hcnt, const int32_t* n_overflow, int bm, int hcap, int64_t n_out, int kv, int c_in,
@@ -420,7 +463,7 @@ int ptc_add_norm_bwd(const float* dz_in, const void* dy, int dy_dtype, const flo
  *   qkv        : [total, 3, H, 16] bf16 (or f16), packed
  *   cu_seqlens : [n_seq+1] int32
  *   out        : [total, H, 16] same dtype ; lse : [H, total] fp32 (natural-log sum-exp)
- * non-causal, no dropout, softmax_scale given.  max_seqlen <= 1024.
+ * non-causal, no dropout, softmax_scale given.  max_seqlen <= PTC_ATTN_MAX_SEQLEN.
  * Backward recomputes P from (q,k,lse):  dqkv [total,3,H,16].
  * ------------------------------------------------------------------------------------------ */
 int ptc_attn_varlen_fwd(const void* qkv, const int32_t* cu_seqlens, int64_t n_seq, int64_t total,
@@ -437,7 +480,7 @@ int ptc_attn_varlen_bwd(const void* qkv, const void* out, const void* dout, cons
  * softmax over all keys, then every probability dropped with probability dropout_p in [0, 1) and the survivors scaled by
  * 1 / (1 - dropout_p); lse is that of the undropped scores).  The mask is a pure function of (seed, sequence, head, query, key) --
  * a 32-bit integer hash compared with dropout_p 2^32 (csrc/attention_drop.h: ad_unit_key / ad_keep; restated in oracle/ops.py) --
- * regenerated by the backward from the same seed; it is NOT flash-attn's Philox stream.  head_dim 16, bf16 or f16 tensors. */
+ * regenerated by the backward from the same seed; it is NOT flash-attn's Philox stream.  head_dim PTC_ATTN_HEAD_DIM, bf16 or f16 tensors. */
 int ptc_attn_varlen_dropout_fwd(const void* qkv, const int32_t* cu_seqlens, int64_t n_seq, int64_t total, int H, int max_seqlen,
                                 float softmax_scale, int dtype, float dropout_p, uint64_t seed, void* out, float* lse,
                                 ptc_stream_t stream);
@@ -449,8 +492,9 @@ int ptc_attn_varlen_dropout_bwd(const void* qkv, const void* out, const void* do
 /* Same operator for head_dim 17..64 (PT-v3m3 / LitePT: head_dim 18, flash_attn_varlen_qkvpacked_func as called at
  * pointcept/models/point_transformer_v3/point_transformer_v3m3_utonia.py:353-359 and pointcept/models/litept/litept_v1.py:244-256):
  *   qkv [total, 3, H, head_dim] bf16 packed, out [total, H, head_dim], lse [H, total] fp32, dqkv like qkv.
- * The window's operands live in LDS, which bounds max_seqlen: head_dim <= 32: 1024, <= 48: 672, <= 64: 512
- * (ptc_attn_varlen_hd_supported returns 1 / 0; the calls return PTC_EUNSUPPORTED outside that range).
+ * The window's operands live in LDS, which bounds max_seqlen: head_dim <= 32: PTC_ATTN_MAX_SEQLEN, <= 48: 672, <= 64: 512
+ * (ptc_attn_varlen_hd_supported returns 1 / 0; the calls return PTC_EUNSUPPORTED outside that range).  The predicate also answers
+ * head_dim PTC_ATTN_HEAD_DIM (the base kernels above: every window up to PTC_ATTN_MAX_SEQLEN), so a caller asks it for any head_dim.
  * The backward's workspace is ptc_attn_varlen_bwd_workspace_bytes(total, H). */
 int ptc_attn_varlen_hd_supported(int head_dim, int max_seqlen);
 int ptc_attn_varlen_hd_fwd(const void* qkv, const int32_t* cu_seqlens, int64_t n_seq, int64_t total,
@@ -489,6 +533,11 @@ int ptc_attn_varlen_hd_rope_bwd(const void* qkv, const void* out, const void* do
  *   16x16x4, fp32 softmax), out / dout / dqkv 16-byte aligned.  The fp32 table gradient uses 2^-44 fixed point (range
  *   +-2^19 per entry); a head whose sum of |dS| over all pairs reaches 2^18 gets NaN in its column of d_rpe_table
  *   instead of a wrapped value. */
+/* ptc_attn_rpe_supported: 1 when the two calls below serve (head_dim, max_seqlen, pos_bnd, dtype) -- head_dim PTC_ATTN_HEAD_DIM, a window
+ * of 1 .. PTC_ATTN_MAX_SEQLEN keys, 0 <= pos_bnd <= PTC_ATTN_RPE_MAX_POS_BND, and the window images, coordinates and table of the
+ * forward AND of the backward within the kernels' LDS budget (the byte counts the launches themselves use); else 0, and both calls
+ * refuse with PTC_EUNSUPPORTED. */
+int ptc_attn_rpe_supported(int head_dim, int max_seqlen, int pos_bnd, int dtype);
 int ptc_attn_rpe_fwd(const void* qkv, const int32_t* cu_seqlens, const int32_t* grid_coord,
                      const float* rpe_table, int pos_bnd, int64_t n_seq, int64_t total, int H,
                      int max_seqlen, float softmax_scale, int dtype, void* out, float* lse,
@@ -526,7 +575,7 @@ int ptc_cross_entropy_bwd(const void* logits, int64_t row_stride, const int64_t*
  * (_lovasz_softmax_flat :118-146, _lovasz_grad :22-33, _flatten_probas :149-166), the second criterion of
  * configs/scannet/semseg-pt-v3m1-0-base.py:49-52, called from pointcept/models/default.py:78-84.
  *   logits [n, c] (row_stride in elements, dtype = ptc_dtype), target [n] int64 (ignore_index / out of range = not
- *   counted), c <= 64.  loss[0] (fp32, DEVICE) = mean over the classes present in the counted labels of
+ *   counted), c <= PTC_LOVASZ_DENSE_MAX_C.  loss[0] (fp32, DEVICE) = mean over the classes present in the counted labels of
  *   <sorted errors, Jaccard steps>; dlogits [n, c] fp32 contiguous = d loss / d logits (0 for uncounted rows).
  *   One segmented radix sort of the [c, n] error matrix; reductions in a fixed order (bit-reproducible).
  *   Ties between equal errors are ordered by ascending point index (the loss does not depend on it). */
@@ -535,7 +584,7 @@ int ptc_lovasz_softmax(const void* logits, int64_t row_stride, const int64_t* ta
                        int64_t ignore_index, float* loss, float* dlogits, void* workspace, size_t workspace_bytes,
                        ptc_stream_t stream);
 
-/* The same loss for 1 <= c <= 1024 classes (ScanNet200: 200, ScanNet++: 100) over the classes PRESENT only: the reference sorts
+/* The same loss for 1 <= c <= PTC_LOVASZ_MAX_C classes (ScanNet200: 200, ScanNet++: 100) over the classes PRESENT only: the reference sorts
  * the classes `labels.unique()` returns (lovasz.py:129-134); a class without a counted label has zero loss and zero
  * probability gradient, so its row of the error matrix is never built.
  * ptc_lovasz_present: class_count [c] = counted labels per class (a label is not counted if it equals ignore_index, is negative
@@ -543,7 +592,7 @@ int ptc_lovasz_softmax(const void* logits, int64_t row_stride, const int64_t* ta
  *   class_of [c] = class of a row (the first P entries; -1 after them), n_present [1] = P.  All int32, DEVICE, on `stream`.
  * ptc_lovasz_softmax_rows: loss and dlogits as ptc_lovasz_softmax, from those four arrays; `rows` = the HOST's copy of P
  *   (it sizes the workspace and the grids; the kernels never use more rows than it).  rows == 0 or n == 0: loss 0, dlogits 0.
- *   c > 1024: PTC_EUNSUPPORTED.  Workspace: keys 8 + order 8 + flags 4 + scan 8 + gprob 4 bytes per (row, point) slot plus
+ *   c > PTC_LOVASZ_MAX_C: PTC_EUNSUPPORTED.  Workspace: keys 8 + order 8 + flags 4 + scan 8 + gprob 4 bytes per (row, point) slot plus
  *   the radix sort's ping-pong buffers (24 bytes per slot + histograms) = ~56 * rows * n bytes (9.2 GB at 819200 x 200 with
  *   every class present, 2.8 GB with 60); 0 when rows == 0 or n == 0.  Integer atomics only, reductions in a fixed order:
  *   bit-reproducible.  Differs from ptc_lovasz_softmax in the summation order of the softmax denominator and of <g, p>. */
@@ -595,20 +644,21 @@ int ptc_ball_query(const float* xyz, const int32_t* offset, const float* new_xyz
  * E = {(t, s) -> j = idx[t * nsample + s]} (idx int32 [m, nsample], -1 = empty slot: gathers zeros, receives no gradient).  fp32 rows,
  * like the reference kernels.  Every gradient of a GATHERED operand is a segmented sum over the edges sorted by source row (fixed
  * order, no atomics) where the reference scatters with atomicAdd.
+ * `mode` is an enumerator of ptc_edge_rows / ptc_edge_reduce / ptc_edge_scatter, see LIMITS, named below without its prefix.
  *   ptc_edge_rows_fwd    per-edge rows into out[e * out_stride + out_col0 .. + c):
- *        mode 0  src[j]          grouping_forward_cuda, libs/pointops/src/grouping/grouping_cuda_kernel.cu:5-15 (functions/grouping.py:8-25)
- *        mode 1  a[t] - src[j]   subtraction_forward_cuda, src/subtraction/subtraction_cuda_kernel.cu:5-17 (functions/subtraction.py:8-22)
- *        mode 2  src[j] - a[t]   (0 for j < 0) the relative coordinates of grouping(with_xyz=True), functions/grouping.py:44-68
+ *        GROUP   src[j]          grouping_forward_cuda, libs/pointops/src/grouping/grouping_cuda_kernel.cu:5-15 (functions/grouping.py:8-25)
+ *        SUB     a[t] - src[j]   subtraction_forward_cuda, src/subtraction/subtraction_cuda_kernel.cu:5-17 (functions/subtraction.py:8-22)
+ *        REL     src[j] - a[t]   (0 for j < 0) the relative coordinates of grouping(with_xyz=True), functions/grouping.py:44-68
  *   ptc_edge_reduce_fwd  per-target sums over the nsample edges of a row, out [m, c]:
- *        mode 0  sum_s w[t,s] src[j]                               interpolation_forward_cuda, src/interpolation/interpolation_cuda_kernel.cu:6-20
- *        mode 1  sum_s (src[j][c] + pos[t,s,c]) w[t,s,c % w_c]     aggregation_forward_cuda, src/aggregation/aggregation_cuda_kernel.cu:5-21
- *        mode 2  sum_s pos[(t,s) * pos_stride + pos_col0 + c]      gradient of subtraction's input1 (subtraction_cuda_kernel.cu:19-33);
+ *        INTERP  sum_s w[t,s] src[j]                               interpolation_forward_cuda, src/interpolation/interpolation_cuda_kernel.cu:6-20
+ *        AGG     sum_s (src[j][c] + pos[t,s,c]) w[t,s,c % w_c]     aggregation_forward_cuda, src/aggregation/aggregation_cuda_kernel.cu:5-21
+ *        POS     sum_s pos[(t,s) * pos_stride + pos_col0 + c]      gradient of subtraction's input1 (subtraction_cuda_kernel.cu:19-33);
  *                idx != NULL: empty slots (idx < 0) are left out of the sum
  *   ptc_edge_csr_keys / ptc_edge_csr_ptr  the edge CSR by source row: keys [E] int64 (j, or n_src for empty slots) for ptc_sort_keys over
  *        bits [0, bit_length(n_src)), then indptr [n_src + 1] int64 from the sorted order (indptr[j] = edges with key < j)
  *   ptc_edge_scatter_bwd grad_src[j] = sum over the edges of source row j, ascending edge index, of coef(e) g[row(e)]:
- *        mode 0 grouping (coef 1, row e), 1 subtraction (coef -1, row e), 2 interpolation (coef w[e], row e / nsample),
- *        mode 3 aggregation (coef w[e, c % w_c], row e / nsample); g rows may be a column window (g_stride, g_col0) of wider rows
+ *        GROUP (coef 1, row e), SUB (coef -1, row e), INTERP (coef w[e], row e / nsample),
+ *        AGG (coef w[e, c % w_c], row e / nsample); g rows may be a column window (g_stride, g_col0) of wider rows
  *        -- grouping_backward_cuda / interpolation_backward_cuda / aggregation_backward_cuda / subtraction_backward_cuda without atomics
  *   ptc_aggregation_edge_bwd  grad_position [m, nsample, c] and grad_weight [m, nsample, w_c] of aggregation
  *        (aggregation_cuda_kernel.cu:23-39; one producer per element) */
@@ -640,7 +690,7 @@ int ptc_pair_segment_sum(const float* s, const float* b, const float* w, const f
 
 /* ------------------------------------------------------------------------------------------
  * J. BatchNorm1d over the rows of [n, c] features with the following activation fused:
- *    y = act((x - mean) * rstd * gamma + beta),  act in {0 none, 1 GELU (erf), 2 ReLU}.
+ *    y = act((x - mean) * rstd * gamma + beta),  act of enum ptc_act: none, GELU in its erf form, ReLU.
  * Replaces `nn.BatchNorm1d(eps=1e-3, momentum=0.01)` + `nn.GELU()` of PTv3's Embedding / SerializedPooling /
  * SerializedUnpooling (ptv3m1:485-515,371-444,447-482; norm built at :581) and BatchNorm1d + ReLU of
  * SpUNet (spconv_unet_v1m1_base.py:49-68,110-121,137-146,173-181).  Per-GPU statistics (sync_bn = False).
@@ -798,14 +848,14 @@ int ptc_cluster_agg_bwd(const void* const* u, const void* const* v, const void* 
  * R. PointGroup clustering and heads (libs/pointgroup_ops: bfs_cluster_kernel.cu:16-61, bfs_cluster.cpp:53-145;
  *    pointcept/models/point_group/point_group_v1m1_base.py:72-91,101-179), csrc/pg_cluster.hip.
  * ptc_pg_ball_query_count / _fill: neighbours of each point i -- same batch index, fp32 d2 (unfused, the reference's order) <
- *   radius*radius, itself included, none for a non-finite coordinate -- in ascending index order, truncated to the first 1000.
+ *   radius*radius, itself included, none for a non-finite coordinate -- in ascending index order, truncated to the first PTC_PG_MAX_NEIGHBOURS.
  *   xyz [n,3] fp32, batch_idxs [n] int32 in [0, n_batch).  count writes start_len [n,2] int32 (exclusive-scan starts, exact lengths)
- *   and total [2] int64 on the device: (nActive, number of truncated lists, i.e. more than 1000 neighbours).  fill writes idx
+ *   and total [2] int64 on the device: (nActive, number of truncated lists, i.e. more than PTC_PG_MAX_NEIGHBOURS neighbours).  fill writes idx
  *   [nActive] int32 and needs the SAME workspace, untouched, after the count.
  * ptc_pg_cluster_count / _fill: bfs_cluster of (label [n] int32, idx, start_len [n,2]) with `threshold`: the reference's clusters,
  *   numbered by seed (their smallest index), members in ascending point order.  count writes counts [2] int32 on the device
  *   (nCluster, sumNPoint); fill writes cluster_idxs [sumNPoint,2] (cluster, point) and cluster_offsets [nCluster+1] int32 from the
- *   same workspace.  A list of >= 1000 entries is taken as possibly truncated (its component follows the sequential rule exactly).
+ *   same workspace.  A list of >= PTC_PG_MAX_NEIGHBOURS entries is taken as possibly truncated (its component follows the sequential rule exactly).
  *   skip_negative != 0: clusters whose seed has a negative label are dropped (the model marks its ignored points so, with no
  *   neighbours, instead of compacting them).
  * ptc_pg_proposal_scores: per cluster k: count[k], cls[k] = label[seed], score[k] = mean over members m of
@@ -840,7 +890,7 @@ int ptc_pg_bias_loss_bwd(const void* bias_pred, int dtype, const float* coord, c
 /* ------------------------------------------------------------------------------------------
  * S. Masked Scene Contrast pretraining (pointcept/models/masked_scene_contrast/masked_scene_contrast_v1m1_base.py:69-203),
  *    csrc/msc.hip.  No float atomics anywhere; every result is bit-reproducible.
- * ptc_msc_match: for each query new_xyz[q] (view 1) the up-to-k (k <= 8) points of the same scene of xyz (view 2) with fp32
+ * ptc_msc_match: for each query new_xyz[q] (view 1) the up-to-k (k <= PTC_MSC_MAX_K) points of the same scene of xyz (view 2) with fp32
  *   sqrt(d2) < max_radius, ascending (d2, index) -- identical to ptc_knn_query(k) followed by `dist < max_radius`.  count [m] int32,
  *   cand [m,k] int32 (-1 padding), stats [2] int32 on the device: (queries with count > 0, largest count).  A non-finite coordinate
  *   matches nothing; m == 0, n == 0 and max_radius <= 0 give empty results.
@@ -1037,7 +1087,7 @@ int ptc_sonata_distill_bwd(const void* teacher, int tdtype, int64_t nt, const vo
 
 /* ------------------------------------------------------------------------------------------
  * Concerto-v1m1 2D-3D alignment branch (csrc/concerto.hip; pointcept/models/concerto/concerto_v1m1_base.py:528-573, :745-866).
- * ptc_concerto_pool_corr: pool_corr for one pooling level and all v images.  corr [n,v,2] (ctype 0 = fp32, 1 = int32, 2 = int64),
+ * ptc_concerto_pool_corr: pool_corr for one pooling level and all v images.  corr [n,v,2] (ctype of enum ptc_corr_type: fp32, int32 or int64),
  *   perm [.] = the points sorted by cluster (NULL: identity), idx_ptr [m+1]; out [m,v,2] fp32.  Per (cluster, image): count = members
  *   with BOTH components != -1; each component summed over ALL members with -1 read as 0 (double, member order of the CSR);
  *   out = sum / count, or (-1, -1) where count == 0.
@@ -1064,9 +1114,9 @@ int ptc_concerto_align(const void* x, int xdtype, int64_t nx, const int64_t* ids
 
 /* ------------------------------------------------------------------------------------------
  * A criteria list of row-local segmentation losses in one pass per direction (csrc/criteria.hip; pointcept/models/losses/misc.py).
- * `flags` selects the terms: 1 = CrossEntropyLoss(weight, label_smoothing, reduction mean | sum), 2 = FocalLoss(gamma, alpha, mean),
- *   4 = DiceLoss(smooth, exponent 1 | 2 | 3); all share ignore_index.  logits [n,c] (fp32 / fp16 / bf16, row stride >= c), target [n]
- *   int64.  c <= 32: any combination; 32 < c <= 1024: flags == 1 only.  A row is counted iff target != ignore_index && 0 <= target < c;
+ * `flags` selects the terms (enum ptc_criteria_term, OR-ed): CE = CrossEntropyLoss(weight, label_smoothing, reduction mean | sum), FOCAL =
+ *   FocalLoss(gamma, alpha, mean), DICE = DiceLoss(smooth, exponent 1 | 2 | 3); all share ignore_index.  logits [n,c] (fp32 / fp16 / bf16, row stride >= c), target [n]
+ *   int64.  c <= PTC_CRITERIA_ROWS_MAX_C: any combination; up to PTC_CRITERIA_CE_MAX_C: PTC_CRITERIA_CE alone.  A row is counted iff target != ignore_index && 0 <= target < c;
  *   the Dice term takes every row with target != ignore_index and clamps its label into [0, c-1], as the reference does.
  *   ce_weight / focal_alpha_vec: [c] fp32 on the device, or NULL (all ones / the scalar focal_alpha).
  * ptc_criteria_partials(n) rows of ptc_criteria_partial_width(c, flags) floats: the per-workgroup partial sums.

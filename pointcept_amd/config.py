@@ -81,8 +81,8 @@ SORT_POINTS = _flag("PTC_SORT_POINTS", True)
 FUSE_BLOCK = _flag("PTC_FUSE_BLOCK", True)
 EXEC_BLOCK = _flag("PTC_EXEC_BLOCK", True)
 FUSE_MLP = _flag("PTC_FUSE_MLP", True)
-CONV8 = _flag("PTC_CONV8", True)                      # also read by the C side (ptc_spconv_fwd_blk)
-MLP_ONE_KERNEL = _flag("PTC_BLK_MLP_FUSED", True)     # the same variable switches the block executor's C side (block_exec.hip)
+# PTC_CONV8 and PTC_BLK_MLP_FUSED are read by the library alone (csrc/conv8.h conv8_enabled, ptc_ptv3_block_mlp_fused); Python asks it
+# (ops.BlockProvider.get, ops.block_mlp_fused): a value beginning with 0 turns the kernel off
 PREFETCH_LEVELS = _flag("PTC_PREFETCH_LEVELS", True)
 RPE_KERNEL = _flag("PTC_RPE_KERNEL", True)
 OACNN_AGG = _flag("PTC_OACNN_AGG", True)

@@ -53,7 +53,7 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 #define AT_WAVES 8
 #define AT_THREADS (AT_WAVES * 64)
-#define AT_MAX_L 1024
+#define AT_MAX_L PTC_ATTN_MAX_SEQLEN
 #define AT_MIN_WAVES 4          // waves per SIMD the register budget must allow (two 8-wave workgroups per CU)
 #define AT_LOG2E 1.4426950408889634f
 #define AT_LN2 0.6931471805599453f
@@ -1071,7 +1071,9 @@ static size_t hd_dq_lds(int dk, int lp_max) { return (size_t)2 * dk * lp_max * 3
 static size_t hd_dkv_lds(int dk, int lp_max) { return (size_t)2 * dk * lp_max * 32 + (size_t)lp_max * 8; }
 
 extern "C" int ptc_attn_varlen_hd_supported(int head_dim, int max_seqlen) {
-  if (head_dim < 17 || head_dim > 64 || max_seqlen < 1 || max_seqlen > AT_MAX_L) return 0;
+  if (max_seqlen < 1 || max_seqlen > AT_MAX_L) return 0;
+  if (head_dim == PTC_ATTN_HEAD_DIM) return 1;      // the base kernels of this file (ptc_attn_varlen_fwd / _bwd): every window up to AT_MAX_L
+  if (head_dim < 17 || head_dim > 64) return 0;
   const int dk = (head_dim + 15) / 16, lp_max = (max_seqlen + 31) & ~31;
   return hd_fwd_lds(dk, head_dim, lp_max) <= AH_LDS_LIMIT && hd_dkv_lds(dk, lp_max) <= AH_LDS_LIMIT;
 }
@@ -1082,9 +1084,8 @@ static int hd_check(const char* name, const void* qkv, const int32_t* cu, int64_
   // f16 I/O around bf16 arithmetic of the head_dim-16 kernels
   int rc = check_common(name, qkv, cu, n_seq, total, H, max_seqlen, dtype, true);
   if (rc != PTC_OK) return rc;
-  PTC_REQUIRE(ptc_attn_varlen_hd_supported(D, max_seqlen), PTC_EUNSUPPORTED,
-              "%s: head_dim=%d with max_seqlen=%d is outside the LDS-resident range (17..32: 1024 keys, ..48: 672, ..64: 512)", name, D,
-              max_seqlen);
+  PTC_REQUIRE(D != PTC_ATTN_HEAD_DIM && ptc_attn_varlen_hd_supported(D, max_seqlen), PTC_EUNSUPPORTED,
+              "%s: head_dim=%d with max_seqlen=%d is outside the LDS-resident range (17..64, ptc_attn_varlen_hd_supported)", name, D, max_seqlen);
   return PTC_OK;
 }
 
@@ -1234,14 +1235,27 @@ extern "C" int ptc_attn_varlen_hd_rope_bwd(const void* qkv, const void* out, con
 // ------------------------------------------------------------------------------------------------
 // relative-position-bias attention, head_dim 16 (attention_rpe.h)
 // ------------------------------------------------------------------------------------------------
+static size_t rpe_fwd_lds(int dtype, int lp_max, int R) {
+  return dtype == PTC_F32 ? ar32_fwd_lds(lp_max, R) : (size_t)lp_max * 32 + (size_t)17 * (lp_max + 8) * 2 + 64 + ar_extra_lds(lp_max, R);
+}
+static size_t rpe_dq_lds(int dtype, int lp_max, int R) { return dtype == PTC_F32 ? ar32_dq_lds(lp_max, R) : (size_t)lp_max * 64 + ar_extra_lds(lp_max, R); }
+static size_t rpe_dkv_lds(int dtype, int lp_max, int R) { return dtype == PTC_F32 ? ar32_dkv_lds(lp_max, R) : (size_t)lp_max * 72 + ar_extra_lds(lp_max, R); }
+extern "C" int ptc_attn_rpe_supported(int head_dim, int max_seqlen, int pos_bnd, int dtype) {
+  if (head_dim != PTC_ATTN_HEAD_DIM || max_seqlen < 1 || max_seqlen > AT_MAX_L || pos_bnd < 0 || pos_bnd > PTC_ATTN_RPE_MAX_POS_BND ||
+      (dtype != PTC_F32 && dtype != PTC_BF16 && dtype != PTC_F16)) return 0;
+  const int lp_max = (max_seqlen + 31) & ~31, R = 2 * pos_bnd + 1;
+  return rpe_fwd_lds(dtype, lp_max, R) <= AH_LDS_LIMIT && rpe_dq_lds(dtype, lp_max, R) <= AH_LDS_LIMIT && rpe_dkv_lds(dtype, lp_max, R) <= AH_LDS_LIMIT;
+}
 static int rpe_check(const char* name, const void* qkv, const int32_t* cu, const int32_t* gc, const float* table, int pos_bnd,
                      int64_t n_seq, int64_t total, int H, int max_seqlen, int dtype) {
   // PTC_F32: the reference's branch without autocast, fp32 arithmetic throughout (attention_rpe_f32.h); bf16 / f16 as check_common
   int rc = dtype == PTC_F32 ? check_shapes(name, qkv, cu, n_seq, total, H, max_seqlen)
                             : check_common(name, qkv, cu, n_seq, total, H, max_seqlen, dtype, true);
   if (rc != PTC_OK) return rc;
-  PTC_REQUIRE(pos_bnd >= 0 && pos_bnd <= 4096, PTC_EINVAL, "%s: pos_bnd=%d out of range", name, pos_bnd);
+  PTC_REQUIRE(pos_bnd >= 0 && pos_bnd <= PTC_ATTN_RPE_MAX_POS_BND, PTC_EINVAL, "%s: pos_bnd=%d out of range", name, pos_bnd);
   PTC_REQUIRE(n_seq == 0 || (gc && table), PTC_EINVAL, "%s: null buffer", name);
+  PTC_REQUIRE(ptc_attn_rpe_supported(PTC_ATTN_HEAD_DIM, max_seqlen, pos_bnd, dtype), PTC_EUNSUPPORTED,
+              "%s: max_seqlen=%d with pos_bnd=%d does not fit LDS (dtype %d)", name, max_seqlen, pos_bnd, dtype);
   return PTC_OK;
 }
 
@@ -1255,9 +1269,7 @@ extern "C" int ptc_attn_rpe_fwd(const void* qkv, const int32_t* cu_seqlens, cons
   const int lp_max = (max_seqlen + 31) & ~31, R = 2 * pos_bnd + 1;
   if (dtype == PTC_F32) {
     PTC_REQUIRE((uintptr_t)out % 16 == 0, PTC_EINVAL, "ptc_attn_rpe_fwd: out must be 16-byte aligned");
-    const size_t lds32 = ar32_fwd_lds(lp_max, R);
-    PTC_REQUIRE(lds32 <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_fwd: max_seqlen=%d with pos_bnd=%d does not fit LDS (fp32)", max_seqlen,
-                pos_bnd);
+    const size_t lds32 = rpe_fwd_lds(dtype, lp_max, R);
     const int n_units = (int)(n_seq * H);
     rc = ptc_allow_lds(attn_rpe_fwd_f32_kernel, lds32);
     if (rc != PTC_OK) return rc;
@@ -1267,8 +1279,7 @@ extern "C" int ptc_attn_rpe_fwd(const void* qkv, const int32_t* cu_seqlens, cons
     PTC_CHECK_LAUNCH("attn_rpe_fwd_f32_kernel");
     return PTC_OK;
   }
-  const size_t lds = (size_t)lp_max * 32 + (size_t)17 * (lp_max + 8) * 2 + 64 + ar_extra_lds(lp_max, R);
-  PTC_REQUIRE(lds <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_fwd: max_seqlen=%d with pos_bnd=%d does not fit LDS", max_seqlen, pos_bnd);
+  const size_t lds = rpe_fwd_lds(dtype, lp_max, R);
   const int n_units = (int)(n_seq * H);
   // F16: the call site's casts (`qkv` of an fp16-autocast Linear -> bf16 operands, output back to fp16) in the load / store paths, as in
   // the flash-branch kernels: configs/s3dis/semseg-pt-v3m1-1-rpe.py runs under the reference's fp16 AMP
@@ -1312,9 +1323,7 @@ extern "C" int ptc_attn_rpe_bwd(const void* qkv, const void* out, const void* do
   if (dtype == PTC_F32) {
     PTC_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)dout % 16 == 0 && (uintptr_t)dqkv % 16 == 0, PTC_EINVAL,
                 "ptc_attn_rpe_bwd: out, dout and dqkv must be 16-byte aligned");
-    const size_t lq = ar32_dq_lds(lp_max, R), lkv = ar32_dkv_lds(lp_max, R);
-    PTC_REQUIRE(lkv <= AH_LDS_LIMIT && lq <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_bwd: max_seqlen=%d with pos_bnd=%d does not fit LDS (fp32)",
-                max_seqlen, pos_bnd);
+    const size_t lq = rpe_dq_lds(dtype, lp_max, R), lkv = rpe_dkv_lds(dtype, lp_max, R);
     float* abs_sum = (float*)((char*)dt_fix + ptc_align_up((size_t)3 * R * H * 8, 256));
     PTC_HIP(hipMemsetAsync(abs_sum, 0, (size_t)H * sizeof(float), s));
     const int n_units = (int)(n_seq * H);
@@ -1337,8 +1346,7 @@ extern "C" int ptc_attn_rpe_bwd(const void* qkv, const void* out, const void* do
     PTC_CHECK_LAUNCH("attn_rpe_bwd_dkv_f32_kernel");
     return PTC_OK;
   }
-  const size_t lds_q = (size_t)lp_max * 64 + ar_extra_lds(lp_max, R), lds_kv = (size_t)lp_max * 72 + ar_extra_lds(lp_max, R);
-  PTC_REQUIRE(lds_kv <= AH_LDS_LIMIT, PTC_EUNSUPPORTED, "ptc_attn_rpe_bwd: max_seqlen=%d with pos_bnd=%d does not fit LDS", max_seqlen, pos_bnd);
+  const size_t lds_q = rpe_dq_lds(dtype, lp_max, R), lds_kv = rpe_dkv_lds(dtype, lp_max, R);
   const int n_units = (int)(n_seq * H);
   const unsigned grid = (unsigned)(8 * ((n_units + 7) / 8));
   float* delta = (float*)workspace;

@@ -27,12 +27,13 @@
 #define AU_THREADS 256
 #define AU_PPT 4                              // points per thread
 #define AU_TILE (AU_THREADS * AU_PPT)         // points per workgroup
-#define AU_MAX_OPS 16                         // affine descriptors per compose launch
-#define AU_MAX_COLOR 8                        // colour ops per flush
+#define AU_MAX_OPS PTC_AUG_MAX_OPS            // affine descriptors per compose launch (ptcore_augment.h)
+#define AU_MAX_COLOR PTC_AUG_MAX_COLOR_OPS     // colour ops per flush
 #define AU_FIN_SLOTS 16
 
-enum { AU_CENTER_SHIFT = 0, AU_ROTATE = 1, AU_SCALE = 2, AU_FLIP = 3, AU_SHIFT = 4 };
-enum { AU_C_AUTOCONTRAST = 0, AU_C_TRANSLATION = 1, AU_C_JITTER = 2, AU_C_NORMALIZE = 3 };
+enum { AU_CENTER_SHIFT = PTC_AUG_CENTER_SHIFT, AU_ROTATE = PTC_AUG_ROTATE, AU_SCALE = PTC_AUG_SCALE, AU_FLIP = PTC_AUG_FLIP, AU_SHIFT = PTC_AUG_SHIFT };
+enum { AU_C_AUTOCONTRAST = PTC_AUG_C_AUTOCONTRAST, AU_C_TRANSLATION = PTC_AUG_C_TRANSLATION, AU_C_JITTER = PTC_AUG_C_JITTER,
+       AU_C_NORMALIZE = PTC_AUG_C_NORMALIZE };
 
 struct AuOps {
   int n;

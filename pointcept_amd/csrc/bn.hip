@@ -16,7 +16,7 @@
 
 #define BN_THREADS 256
 #define BN_MAX_GROUPS 1024
-enum { BN_ACT_NONE = 0, BN_ACT_GELU = 1, BN_ACT_RELU = 2 };
+enum { BN_ACT_NONE = PTC_ACT_NONE, BN_ACT_GELU = PTC_ACT_GELU, BN_ACT_RELU = PTC_ACT_RELU };
 
 template <typename T> struct BnVec;
 template <> struct BnVec<float> { static constexpr int V = 4; };
@@ -382,7 +382,7 @@ static int bn_act_fwd_impl(const void* x, const void* res, int64_t n, int c, int
                            ptc_stream_t stream) {
   PTC_REQUIRE(n >= 0 && ptc_batch_norm_supported(c, dtype), PTC_EUNSUPPORTED, "ptc_batch_norm_act_fwd: n=%lld c=%d dtype=%d unsupported",
               (long long)n, c, dtype);
-  PTC_REQUIRE(act >= 0 && act <= 2, PTC_EINVAL, "ptc_batch_norm_act_fwd: bad activation %d", act);
+  PTC_REQUIRE(act >= BN_ACT_NONE && act <= BN_ACT_RELU, PTC_EINVAL, "ptc_batch_norm_act_fwd: bad activation %d", act);
   PTC_REQUIRE(training || (running_mean && running_var), PTC_EINVAL, "ptc_batch_norm_act_fwd: eval mode needs running statistics");
   PTC_REQUIRE(y_dtype == dtype || y_dtype == PTC_F32 || dtype == PTC_F32, PTC_EUNSUPPORTED, "ptc_batch_norm_act_fwd: dtype pair");
   if (n == 0) return PTC_OK;
@@ -465,7 +465,7 @@ static int bn_act_bwd_impl(const void* dy, int dy_dtype, const void* x, const vo
                            ptc_stream_t stream) {
   PTC_REQUIRE(n >= 0 && ptc_batch_norm_supported(c, x_dtype), PTC_EUNSUPPORTED, "ptc_batch_norm_act_bwd: n=%lld c=%d dtype=%d unsupported",
               (long long)n, c, x_dtype);
-  PTC_REQUIRE(act >= 0 && act <= 2, PTC_EINVAL, "ptc_batch_norm_act_bwd: bad activation %d", act);
+  PTC_REQUIRE(act >= BN_ACT_NONE && act <= BN_ACT_RELU, PTC_EINVAL, "ptc_batch_norm_act_bwd: bad activation %d", act);
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) {
     if (dgamma) PTC_HIP(hipMemsetAsync(dgamma, 0, (size_t)c * sizeof(float), s));

@@ -248,15 +248,15 @@ static inline unsigned cc_grid(int64_t total) {
 extern "C" int ptc_concerto_pool_corr(const void* corr, int ctype, int64_t n, int v, const int64_t* perm, const int64_t* idx_ptr, int64_t m,
                                       float* out, ptc_stream_t stream) {
   PTC_REQUIRE(n >= 0 && m >= 0 && v >= 0, PTC_EINVAL, "ptc_concerto_pool_corr: n=%lld m=%lld v=%d", (long long)n, (long long)m, v);
-  PTC_REQUIRE(ctype >= 0 && ctype <= 2, PTC_EINVAL, "ptc_concerto_pool_corr: correspondence type %d (0 fp32, 1 int32, 2 int64)", ctype);
+  PTC_REQUIRE(ctype >= PTC_CORR_F32 && ctype <= PTC_CORR_I64, PTC_EINVAL, "ptc_concerto_pool_corr: correspondence type %d (enum ptc_corr_type)", ctype);
   PTC_REQUIRE(m * (int64_t)v < ((int64_t)1 << 31) * CC_THREADS, PTC_EINVAL, "ptc_concerto_pool_corr: too many (cluster, image) pairs");
   if (m == 0 || v == 0) return PTC_OK;
   PTC_REQUIRE((corr || n == 0) && idx_ptr && out, PTC_EINVAL, "ptc_concerto_pool_corr: null buffer");
   hipStream_t st = (hipStream_t)stream;
   const unsigned g = cc_grid(m * v);
-  if (ctype == 0)
+  if (ctype == PTC_CORR_F32)
     hipLaunchKernelGGL(cc_pool_corr_kernel<float>, dim3(g), dim3(CC_THREADS), 0, st, (const float*)corr, n, v, perm, idx_ptr, m, out);
-  else if (ctype == 1)
+  else if (ctype == PTC_CORR_I32)
     hipLaunchKernelGGL(cc_pool_corr_kernel<int32_t>, dim3(g), dim3(CC_THREADS), 0, st, (const int32_t*)corr, n, v, perm, idx_ptr, m, out);
   else
     hipLaunchKernelGGL(cc_pool_corr_kernel<int64_t>, dim3(g), dim3(CC_THREADS), 0, st, (const int64_t*)corr, n, v, perm, idx_ptr, m, out);

@@ -57,14 +57,15 @@
 #ifndef C7_LAG
 #define C7_LAG 2                            // MFMAs between a fragment's use and its reload (C = 64; 3 and 4 measured: see conv7_time)
 #endif
-#define C7_BM 128                           // rows per block
+#define C7_BM PTC_BLOCK_BM                  // rows per block (include/ptcore.h, LIMITS)
 #define C7_NT 8                             // 16-row tiles per block
-#define C7_HCAP 416                         // halo capacity (rows); max observed on curve-ordered indoor scenes: 352
+#define C7_HCAP PTC_BLOCK_HCAP              // halo capacity (rows); max observed on curve-ordered indoor scenes: 352
 #define C7_TABB (28 * 16 * C7_NT * 2)       // bytes of one block's local table: [28 taps (27 + pad)][16 rows-in-tile][8 tiles] u16, each
                                             // entry = LDS byte offset of piece 0 of the neighbour row inside the row image (blocks.hip)
 
+#define C7_MIN_ROWS 4096                    // fewer rows stay on the global-gather kernels (ptc_spconv_blk_min_rows reports it)
 static inline bool conv7_supported(int dtype, int kv, int c_in, int c_out, int bm, int hcap, int64_t n_out) {
-  return dtype != PTC_F32 && kv == 27 && c_in == c_out && (c_in == 32 || c_in == 64) && bm == C7_BM && hcap == C7_HCAP && n_out >= 4096;
+  return dtype != PTC_F32 && kv == 27 && c_in == c_out && (c_in == 32 || c_in == 64) && bm == C7_BM && hcap == C7_HCAP && n_out >= C7_MIN_ROWS;
 }
 
 

@@ -81,14 +81,17 @@ __device__ __forceinline__ uint32_t c8_lds_addr(const void* p) { return (uint32_
 #endif
 
 static inline size_t conv8_lds(int rt) { return (size_t)C8_TAB_BYTES + (size_t)(c8_himg(rt) + 1) * C8_PITCH + (size_t)c8_passes(rt) * 32 * 4; }   // table | image | halo list
+#define C8_MIN_ROWS 256      // fewer rows stay on conv3
 static inline bool conv8_supported(int dtype, int kv, int c_in, int c_out, int bm, int hcap, int64_t n_out) {
-  return dtype != PTC_F32 && kv == 27 && c_in % 32 == 0 && c_in >= 96 && c_in <= 1024 && c_out % 32 == 0 && c_out <= 1024 && bm == 128 && hcap >= 16 &&
-         hcap <= 511 && n_out >= 256;
+  return dtype != PTC_F32 && kv == 27 && c_in % 32 == 0 && c_in >= 96 && c_in <= 1024 && c_out % 32 == 0 && c_out <= 1024 && bm == C7_BM && hcap >= 16 &&
+         hcap <= 511 && n_out >= C8_MIN_ROWS;
 }
+// PTC_CONV8=0 keeps the wide shapes on conv3's global gathers: read here alone, per call
+static inline bool conv8_enabled() { const char* e = getenv("PTC_CONV8"); return !(e && e[0] == '0'); }
 // the caller's workspace holds the fragment-ordered weights (16-bit).  A function of the channel counts alone -- not of dtype, tables or
 // PTC_CONV8 -- so that a caller may cache it per shape: 0 wherever conv8_supported says no for every dtype
 static inline size_t conv8_workspace_bytes(int kv, int c_in, int c_out) {
-  if (!conv8_supported(PTC_BF16, kv, c_in, c_out, 128, 416, 256)) return 0;
+  if (!conv8_supported(PTC_BF16, kv, c_in, c_out, C7_BM, C7_HCAP, C8_MIN_ROWS)) return 0;
   return ptc_align_up((size_t)c_out * 27 * c_in * 2, 256);
 }
 // columns per workgroup: 128 | 96 (every wave all 128 rows of the block), 64 (two waves per 64-row half), 32 (a wave per 32 rows) -- the
@@ -377,7 +380,7 @@ conv8_kernel(const T* __restrict__ in, const T* __restrict__ wf, const float* __
 template <typename T, int RT>
 static int launch_conv8_i(const void* in, int64_t n_in, const void* wf, const float* bias, const uint16_t* tab, const int32_t* hid, const int32_t* hcnt,
                           int hcap, int64_t n, int c_in, int c_out, int nt, void* out, hipStream_t s) {
-  const int n_blocks = (int)ptc_cdiv(n, 128);
+  const int n_blocks = (int)ptc_cdiv(n, C7_BM);
   const int nblk = n_blocks * (c_out / nt);
   const size_t lds = conv8_lds(RT);
   auto kern = conv8_kernel<T, RT>;
@@ -395,7 +398,7 @@ static int launch_conv8(const void* in, int64_t n_in, const void* w, const float
   const int64_t pieces = (int64_t)wbytes / 16;
   hipLaunchKernelGGL((conv8_wfrag_kernel<T>), dim3((unsigned)(pieces / 256 < 2048 ? ptc_cdiv(pieces, 256) : 2048)), dim3(256), 0, s, (const T*)w, c_out, c_in, (T*)wf);
   PTC_CHECK_LAUNCH("conv8_wfrag_kernel");
-  const int nt = conv8_nt(c_out, ptc_cdiv(n, 128));
+  const int nt = conv8_nt(c_out, ptc_cdiv(n, C7_BM));
   int rc;
   if (nt >= 96) rc = launch_conv8_i<T, 4>(in, n_in, wf, bias, tab, hid, hcnt, hcap, n, c_in, c_out, nt, out, s);
   else if (nt == 64) rc = launch_conv8_i<T, 2>(in, n_in, wf, bias, tab, hid, hcnt, hcap, n, c_in, c_out, nt, out, s);

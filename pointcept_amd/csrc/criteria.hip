@@ -18,14 +18,14 @@
 //      finish kernel leaves ca_c = 2 / (C den_c) and cb_c = e num_c / (C den_c^2); q_c = cb_c p_c^(e-1) - ca_c [t==c] is dL/dp_c and
 //      the row applies the softmax Jacobian p_c (q_c - sum_k p_k q_k).
 // No atomics anywhere: run-to-run bit-reproducible.  No host read: the means' denominators stay on the device (ptc_criteria_finish).
-// 32 < C <= 1024: term a alone, on element-wise kernels in the style of loss.hip's ce_fwd_kernel / ce_bwd_kernel.
+// LR_CP < C <= PTC_CRITERIA_CE_MAX_C: term a alone, on element-wise kernels in the style of loss.hip's ce_fwd_kernel / ce_bwd_kernel.
 #include "ptc_common.h"
 #include "loss_rows.h"
 #include <math.h>
 
-#define CR_CE 1
-#define CR_FOCAL 2
-#define CR_DICE 4
+#define CR_CE PTC_CRITERIA_CE          // enum ptc_criteria_term (include/ptcore.h)
+#define CR_FOCAL PTC_CRITERIA_FOCAL
+#define CR_DICE PTC_CRITERIA_DICE
 #define CR_HEAD 4          // partial row: ce loss, ce denominator, focal sum, focal rows; then with CR_DICE A[c], B[c], T[c]
 #define CR_GROUPS 8        // the Dice column sums: 8 groups of 32 rows
 
@@ -245,7 +245,7 @@ crit_bwd_rows_kernel(const T* __restrict__ logits, int64_t row_stride, const int
   lr_copy_out<T>(smem, dlogits + row0 * c, (int)rows * c, a16 != 0);
 }
 
-// 32 < C <= 1024: term a alone, element-wise over the row in global memory (three passes, as ce_fwd_kernel)
+// LR_CP < C <= PTC_CRITERIA_CE_MAX_C: term a alone, element-wise over the row in global memory (three passes, as ce_fwd_kernel)
 template <typename T>
 __global__ void __launch_bounds__(256)
 crit_ce_fwd_kernel(const T* __restrict__ logits, int64_t row_stride, const int64_t* __restrict__ target, int64_t n, CrArgs a,
@@ -364,7 +364,8 @@ static inline size_t cr_fwd_lds(int c, int flags) {
 }
 
 static int cr_check(const char* who, int64_t n, int c, int64_t row_stride, int flags, int dice_exp) {
-  PTC_REQUIRE(n >= 0 && c >= 1 && c <= 1024 && row_stride >= c, PTC_EINVAL, "%s: bad sizes", who);
+  PTC_REQUIRE(n >= 0 && c >= 1 && row_stride >= c, PTC_EINVAL, "%s: bad sizes", who);
+  PTC_REQUIRE(c <= PTC_CRITERIA_CE_MAX_C, PTC_EINVAL, "%s: %d classes (at most %d)", who, c, PTC_CRITERIA_CE_MAX_C);
   PTC_REQUIRE(flags > 0 && flags <= (CR_CE | CR_FOCAL | CR_DICE), PTC_EINVAL, "%s: bad term flags %d", who, flags);
   PTC_REQUIRE(c <= LR_CP || flags == CR_CE, PTC_EINVAL, "%s: more than %d classes take the cross-entropy term alone", who, LR_CP);
   PTC_REQUIRE(!(flags & CR_DICE) || (dice_exp >= 1 && dice_exp <= 3), PTC_EINVAL, "%s: Dice exponent %d (1, 2 or 3)", who, dice_exp);

@@ -11,7 +11,7 @@
 // (C > LR_CP: CrossEntropyLoss serves up to 1024 classes) keep the element-wise kernels.
 #pragma once
 
-#define LR_CP 32
+#define LR_CP PTC_CRITERIA_ROWS_MAX_C
 #define LR_THREADS 256
 
 // VB = bytes per load instruction: 16 | 8 | 0 (element-wise).  Elements past c inside the last vector are loaded (the host checked that

@@ -29,7 +29,7 @@
 #include "loss_rows.h"
 
 #define LV_THREADS 256
-#define LV_MAX_C 64
+#define LV_MAX_C PTC_LOVASZ_DENSE_MAX_C
 #define LV_ONE 0x3f800000u
 #define LV_STEP_BLOCKS 4096
 
@@ -349,7 +349,7 @@ extern "C" int ptc_lovasz_softmax(const void* logits, int64_t row_stride, const 
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
-// Row-compacted path, 1 <= c <= 1024 (ScanNet200: 200 classes, ScanNet++: 100).  The reference sorts only the classes labels.unique()
+// Row-compacted path, 1 <= c <= LW_MAX_C (ScanNet200: 200 classes, ScanNet++: 100).  The reference sorts only the classes labels.unique()
 // returns; a class without a counted point has zero loss and zero probability gradient, so its row of the [c, n] error matrix never
 // exists here: the P present classes get the compact rows 0..P-1 in ascending class order (ptc_lovasz_present), and keys, sort, scan,
 // steps and gprob are [P, n] -- ~56 B per slot of workspace where the dense layout above would take 9 GB at 819200 x 200.
@@ -365,7 +365,7 @@ extern "C" int ptc_lovasz_softmax(const void* logits, int64_t row_stride, const 
 // The tile's point count shrinks as c grows (LW_TILE_BYTES per tile: 64 points up to 120 classes, 32 up to 248, 16 up to 504, 8 up to 1016) instead of
 // the class axis being cut into chunks: a chunked class axis needs the row's maximum and sum before its first chunk's probabilities,
 // i.e. a second evaluation of every exp.
-#define LW_MAX_C 1024
+#define LW_MAX_C PTC_LOVASZ_MAX_C
 #define LW_RV 16                       // registers of one lane holding its share of a row: 64 lanes x 16 = 1024 classes
 #define LW_TILE_BYTES (32 * 1024)         // two images (dlogits) stay inside the 64 KB a launch gets without opting in
 

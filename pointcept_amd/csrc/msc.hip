@@ -1,7 +1,7 @@
 // msc.hip -- Masked Scene Contrast pretraining (pointcept/models/masked_scene_contrast/masked_scene_contrast_v1m1_base.py): the three
 // stretches of the wrapper around the backbone.
 //
-// 1  Radius-bounded nearest matches (match_contrastive_pair, :144-162).  For a query of view 1 the up-to-k (k <= 8) points of the same
+// 1  Radius-bounded nearest matches (match_contrastive_pair, :144-162).  For a query of view 1 the up-to-k (k <= PTC_MSC_MAX_K) points of the same
 //    scene of view 2 with fp32 sqrt(d2) < max_radius, ascending (d2, index): exactly ptc_knn_query(8, ...) followed by the reference's
 //    `distance < max_radius` ("k nearest, then filter" and "filter, then k nearest" pick the same set).  d2 is pointops.hip's unfused
 //    expression and the root is taken as ptc_knn_query takes it.  View 2 is sorted (ptc_sort_keys, stable: ascending index inside a
@@ -24,7 +24,7 @@
 #include "mma.h"
 
 #define MSC_THREADS 256
-#define MSC_KMAX 8
+#define MSC_KMAX PTC_MSC_MAX_K
 
 namespace {
 

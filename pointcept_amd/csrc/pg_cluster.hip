@@ -21,7 +21,7 @@
 // 4  Bias losses (masked L1 + negative cosine) forward as two fixed-order reduction levels, and their backward in one pass.
 #include "cell_grid.h"
 
-#define PG_MAX_NBR 1000
+#define PG_MAX_NBR PTC_PG_MAX_NEIGHBOURS
 #define PG_THREADS 256
 #define PG_SENTINEL 0x7fffffffffffffffll
 

@@ -284,10 +284,10 @@ extern "C" {
 
 int ptc_edge_rows_fwd(int mode, const float* src, const float* a, const int32_t* idx, int64_t n_edges, int nsample, int c,
                       int64_t n_src, float* out, int64_t out_stride, int out_col0, ptc_stream_t stream) {
-  if (mode < 0 || mode > 2 || n_edges < 0 || nsample <= 0 || c <= 0 || n_src < 0 || out_stride < out_col0 + c || out_col0 < 0)
+  if (mode < PTC_EDGE_ROWS_GROUP || mode > PTC_EDGE_ROWS_REL || n_edges < 0 || nsample <= 0 || c <= 0 || n_src < 0 || out_stride < out_col0 + c || out_col0 < 0)
     { ptc_set_error("ptc_edge_rows_fwd: bad shape"); return PTC_EINVAL; }
   if (n_edges == 0) return PTC_OK;
-  if (!src || !idx || !out || (mode != 0 && !a)) { ptc_set_error("ptc_edge_rows_fwd: null pointer"); return PTC_EINVAL; }
+  if (!src || !idx || !out || (mode != PTC_EDGE_ROWS_GROUP && !a)) { ptc_set_error("ptc_edge_rows_fwd: null pointer"); return PTC_EINVAL; }
   hipLaunchKernelGGL(edge_rows_fwd_kernel, dim3(eg_grid(n_edges * ((c + 3) / 4))), dim3(EG_THREADS), 0, (hipStream_t)stream, mode, src, a, idx, n_edges, nsample, c,
                                                                                                  n_src, out, out_stride, out_col0);
   PTC_CHECK_LAUNCH("ptc_edge_rows_fwd");
@@ -296,11 +296,11 @@ int ptc_edge_rows_fwd(int mode, const float* src, const float* a, const int32_t*
 
 int ptc_edge_reduce_fwd(int mode, const float* src, const float* pos, int64_t pos_stride, int pos_col0, const float* w,
                         const int32_t* idx, int64_t m, int nsample, int c, int w_c, int64_t n_src, float* out, ptc_stream_t stream) {
-  if (mode < 0 || mode > 2 || m < 0 || nsample <= 0 || c <= 0 || n_src < 0) { ptc_set_error("ptc_edge_reduce_fwd: bad shape"); return PTC_EINVAL; }
-  if (mode == 1 && (w_c <= 0 || c % w_c != 0)) { ptc_set_error("ptc_edge_reduce_fwd: c must be a multiple of w_c"); return PTC_EINVAL; }
-  if (mode == 2 && (pos_col0 < 0 || pos_stride < pos_col0 + c)) { ptc_set_error("ptc_edge_reduce_fwd: bad column window"); return PTC_EINVAL; }
+  if (mode < PTC_EDGE_REDUCE_INTERP || mode > PTC_EDGE_REDUCE_POS || m < 0 || nsample <= 0 || c <= 0 || n_src < 0) { ptc_set_error("ptc_edge_reduce_fwd: bad shape"); return PTC_EINVAL; }
+  if (mode == PTC_EDGE_REDUCE_AGG && (w_c <= 0 || c % w_c != 0)) { ptc_set_error("ptc_edge_reduce_fwd: c must be a multiple of w_c"); return PTC_EINVAL; }
+  if (mode == PTC_EDGE_REDUCE_POS && (pos_col0 < 0 || pos_stride < pos_col0 + c)) { ptc_set_error("ptc_edge_reduce_fwd: bad column window"); return PTC_EINVAL; }
   if (m == 0) return PTC_OK;
-  if (!out || (mode != 2 && (!src || !idx || !w)) || (mode != 0 && !pos)) { ptc_set_error("ptc_edge_reduce_fwd: null pointer"); return PTC_EINVAL; }
+  if (!out || (mode != PTC_EDGE_REDUCE_POS && (!src || !idx || !w)) || (mode != PTC_EDGE_REDUCE_INTERP && !pos)) { ptc_set_error("ptc_edge_reduce_fwd: null pointer"); return PTC_EINVAL; }
   hipLaunchKernelGGL(edge_reduce_fwd_kernel, dim3(eg_grid(m * ((c + 3) / 4))), dim3(EG_THREADS), 0, (hipStream_t)stream, mode, src, pos, pos_stride, pos_col0, w, idx, m,
                                                                                              nsample, c, w_c > 0 ? w_c : 1, n_src, out);
   PTC_CHECK_LAUNCH("ptc_edge_reduce_fwd");
@@ -326,11 +326,11 @@ int ptc_edge_csr_ptr(const int64_t* keys, const int64_t* order, int64_t n_edges,
 
 int ptc_edge_scatter_bwd(int mode, const int64_t* order, const int64_t* indptr, const float* g, int64_t g_stride, int g_col0,
                          const float* w, int nsample, int c, int w_c, int64_t n_src, float* grad_src, ptc_stream_t stream) {
-  if (mode < 0 || mode > 3 || nsample <= 0 || c <= 0 || n_src < 0 || g_col0 < 0 || g_stride < g_col0 + c)
+  if (mode < PTC_EDGE_SCATTER_GROUP || mode > PTC_EDGE_SCATTER_AGG || nsample <= 0 || c <= 0 || n_src < 0 || g_col0 < 0 || g_stride < g_col0 + c)
     { ptc_set_error("ptc_edge_scatter_bwd: bad shape"); return PTC_EINVAL; }
-  if (mode == 3 && (w_c <= 0 || c % w_c != 0)) { ptc_set_error("ptc_edge_scatter_bwd: c must be a multiple of w_c"); return PTC_EINVAL; }
+  if (mode == PTC_EDGE_SCATTER_AGG && (w_c <= 0 || c % w_c != 0)) { ptc_set_error("ptc_edge_scatter_bwd: c must be a multiple of w_c"); return PTC_EINVAL; }
   if (n_src == 0) return PTC_OK;
-  if (!order || !indptr || !g || !grad_src || (mode >= 2 && !w)) { ptc_set_error("ptc_edge_scatter_bwd: null pointer"); return PTC_EINVAL; }
+  if (!order || !indptr || !g || !grad_src || (mode >= PTC_EDGE_SCATTER_INTERP && !w)) { ptc_set_error("ptc_edge_scatter_bwd: null pointer"); return PTC_EINVAL; }
   hipLaunchKernelGGL(edge_scatter_bwd_kernel, dim3(eg_grid(n_src * ((c + 3) / 4))), dim3(EG_THREADS), 0, (hipStream_t)stream, mode, order, indptr, g, g_stride, g_col0, w,
                                                                                                   nsample, c, w_c > 0 ? w_c : 1, n_src,
                                                                                                   grad_src);

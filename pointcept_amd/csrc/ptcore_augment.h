@@ -19,6 +19,11 @@ extern "C" {
 #define PTC_AUG_ABI 1
 int64_t ptc_aug_abi(void);
 
+#define PTC_AUG_MAX_OPS 16            /* limits and kinds, their one definition: affine descriptors per ptc_aug_compose call */
+#define PTC_AUG_MAX_COLOR_OPS 8       /* colour ops per ptc_aug_apply call */
+enum ptc_aug_kind { PTC_AUG_CENTER_SHIFT = 0, PTC_AUG_ROTATE = 1, PTC_AUG_SCALE = 2, PTC_AUG_FLIP = 3, PTC_AUG_SHIFT = 4 };
+enum ptc_aug_color_kind { PTC_AUG_C_AUTOCONTRAST = 0, PTC_AUG_C_TRANSLATION = 1, PTC_AUG_C_JITTER = 2, PTC_AUG_C_NORMALIZE = 3 };
+
 /* ------------------------------------------------------------------------------------------
  * Device-side point augmentation (csrc/augment.hip; pointcept/datasets/transform.py:143-451, :779-836).
  * State of one scene, on the device in double: aff [21] = A [3x3] row-major, t [3], Rn [3x3] (coord' = A p + t, normal' = Rn n) and
@@ -27,7 +32,7 @@ int64_t ptc_aug_abi(void);
  *   Nothing here synchronises or reads device memory on the host; min / max are exact, no atomics: bit-reproducible.
  * ptc_aug_reduce: stats[0..6) = box of A p + t when coord != NULL, stats[6..12) = channel min / max when color != NULL; the other
  *   half of stats keeps its values.
- * ptc_aug_compose: ops = HOST [n_ops, 8] doubles (n_ops <= 16), each row kind then arguments:
+ * ptc_aug_compose: ops = HOST [n_ops, 8] doubles (n_ops <= PTC_AUG_MAX_OPS), each row kind (enum ptc_aug_kind) then arguments:
  *     0 CenterShift(apply_z)                      shift by -((xmin+xmax)/2, (ymin+ymax)/2, apply_z ? zmin : 0)             needs stats
  *     1 Rotate(axis 0|1|2, cos, sin, given, cx, cy, cz)  about the given centre, or (given == 0) the box centre            needs stats
  *     2 Scale(sx, sy, sz)     3 Flip(x, y)     4 Shift(dx, dy, dz)
@@ -37,7 +42,7 @@ int64_t ptc_aug_abi(void);
  *     coord_out = A p + t, evaluated in double, + clip(sigma z, -clip, clip) when jitter != 0 (z = jitter_noise [n,3], or NULL: the
  *       generator with (jitter_seed, stream 0)), rounded once, then clamped to clip_range (HOST [6] = min xyz, max xyz; NULL: none).
  *     normal_out = Rn n.
- *     color_out = the n_color_ops <= 8 ops of color_ops (HOST [n,6] doubles: kind, p0, p1, p2, seed < 2^53, stream) in order, fp32:
+ *     color_out = the n_color_ops <= PTC_AUG_MAX_COLOR_OPS ops of color_ops (HOST [n,6] doubles: kind (enum ptc_aug_color_kind), p0, p1, p2, seed < 2^53, stream) in order, fp32:
  *       0 AutoContrast(blend): lo / hi = stats[6..12); scale 255 / (hi - lo), 1 on a channel with hi == lo; untouched when no channel
  *         differs; (1 - blend) c + blend (c - lo) scale       1 Translation(r, g, b): clip(t + c, 0, 255)
  *       2 Jitter(std * 255): clip(z p0 + c, 0, 255), z = color_noise[i] [n,3] (HOST array of n_color_ops device pointers, or NULL) or

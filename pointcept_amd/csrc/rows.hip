@@ -82,13 +82,16 @@ gather_rows_add_kernel(const T* __restrict__ src, const int64_t* __restrict__ id
   }
 }
 
+extern "C" int ptc_gather_rows_add_supported(int c, int dtype) {      // rows of whole 16-byte lanes: the kernel moves one lane per thread
+  return (dtype == PTC_F32 || dtype == PTC_F16 || dtype == PTC_BF16) && c >= 1 && c % (dtype == PTC_F32 ? 4 : 8) == 0;
+}
 extern "C" int ptc_gather_rows_add(const void* src, int64_t n_src, const int64_t* idx, const void* addend, int64_t n_out, int c, int dtype,
                                    void* out, ptc_stream_t stream) {
   PTC_REQUIRE(n_src >= 0 && n_out >= 0 && c >= 1, PTC_EINVAL, "ptc_gather_rows_add: bad sizes");
   if (n_out == 0) return PTC_OK;
   PTC_REQUIRE(src && idx && addend && out, PTC_EINVAL, "ptc_gather_rows_add: null buffer");
   const int w = dtype == PTC_F32 ? 4 : 8;
-  PTC_REQUIRE(c % w == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)addend % 16 == 0 && (uintptr_t)out % 16 == 0, PTC_EUNSUPPORTED,
+  PTC_REQUIRE(ptc_gather_rows_add_supported(c, dtype) && (uintptr_t)src % 16 == 0 && (uintptr_t)addend % 16 == 0 && (uintptr_t)out % 16 == 0, PTC_EUNSUPPORTED,
               "ptc_gather_rows_add: rows of whole 16-byte lanes only (c=%d)", c);
   int64_t grid = ptc_cdiv(n_out * (c / w), 256);
   if (grid > 256 * 32) grid = 256 * 32;

@@ -10,10 +10,6 @@
 #include "voxel_hash.h"
 #include <stdlib.h>
 
-extern "C" int ptc_sort_keys(const int64_t*, int64_t, int, int, int, int64_t*, int64_t*, void*, size_t, ptc_stream_t);
-extern "C" size_t ptc_sort_keys_workspace_bytes(int64_t, int);
-extern "C" size_t ptc_exclusive_scan_workspace_bytes(int64_t);
-extern "C" int ptc_exclusive_scan_i32(const int32_t*, int64_t, int64_t*, void*, size_t, ptc_stream_t);
 
 // ---- voxel table: open addressing over BUCKETS of 2x2x2 voxels ------------------------------------
 // One 64-byte bucket = { block key (b, x>>1, y>>1, z>>1) | 8 row indices, one per voxel of the block }.

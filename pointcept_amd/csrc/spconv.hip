@@ -259,17 +259,24 @@ extern "C" size_t ptc_spconv_fwd_blk_workspace_bytes(int64_t n_out, int kv, int 
   (void)n_out;      // (an upper bound over the row counts: calls below conv8's 256 rows need none)
   return conv8_workspace_bytes(kv, c_in, c_out);
 }
+// the row count from which `consumer` takes standard tables, -1 = never: the launch paths' predicates at the thresholds they name, ascending
+extern "C" int64_t ptc_spconv_blk_min_rows(int consumer, int kv, int c_in, int c_out, int dtype) {
+  const int64_t thresholds[] = {C8_MIN_ROWS, W7_SLICED_MIN_ROWS, C7_MIN_ROWS};
+  for (const int64_t rows : thresholds) {
+    if (consumer == PTC_CONSUMER_CONV7 ? conv7_supported(dtype, kv, c_in, c_out, C7_BM, C7_HCAP, rows)
+        : consumer == PTC_CONSUMER_CONV8 ? conv8_enabled() && conv8_supported(dtype, kv, c_in, c_out, C7_BM, C7_HCAP, rows)
+                                         : consumer == PTC_CONSUMER_WGRAD7 && wgrad7_supported(dtype, kv, c_in, c_out, C7_BM, C7_HCAP, rows))
+      return rows;
+  }
+  return -1;
+}
 extern "C" int ptc_spconv_fwd_blk(const void* in, int64_t n_in, const void* weight, const float* bias, const int32_t* nbr,
                                   const void* tab, const int32_t* hid, const int32_t* hcnt, int bm, int hcap, int64_t n_out, int kv,
                                   int c_in, int c_out, int dtype, void* out, void* workspace, size_t workspace_bytes, ptc_stream_t stream) {
   const bool buf_ok = (uint64_t)n_in * (uint64_t)c_in * ptc_dtype_size(dtype) <= PTC_BUF_MAX_BYTES;
   // round 6: the wide shapes (c_in >= 96) on the block-staged kernel with streamed weights (conv8.h), its fragment-ordered weights in the
-  // caller's workspace -- ON BY DEFAULT, forward and input gradient; PTC_CONV8=0 in the environment keeps these shapes on conv3's global
-  // gathers (pointcept_amd/config.py; profiles/r06_t_conv8_himg.txt, conv8.h's head and DESIGN 4.2 have the measurements).  Tested by
-  // tests/test_gpu_kernels.py::test_spconv_fwd_block_staged_wide
-  const char* c8e = getenv("PTC_CONV8");
-  const bool conv8_on = !(c8e && c8e[0] == '0');
-  if (conv8_on && buf_ok && tab && hid && hcnt && nbr && n_in == n_out && conv8_supported(dtype, kv, c_in, c_out, bm, hcap, n_out)) {
+  // caller's workspace -- on unless conv8_enabled() says no.  Tested by tests/test_gpu_kernels.py::test_spconv_fwd_block_staged_wide
+  if (conv8_enabled() && buf_ok && tab && hid && hcnt && nbr && n_in == n_out && conv8_supported(dtype, kv, c_in, c_out, bm, hcap, n_out)) {
     PTC_REQUIRE(weight && out && in, PTC_EINVAL, "ptc_spconv_fwd_blk: null buffer");
     PTC_REQUIRE(workspace && workspace_bytes >= conv8_workspace_bytes(kv, c_in, c_out), PTC_EWORKSPACE, "ptc_spconv_fwd_blk: workspace too small");
     PTC_REQUIRE(((uintptr_t)in % 16 == 0) && ((uintptr_t)weight % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)tab % 16 == 0) &&

@@ -1,17 +1,16 @@
 // voxel_hash.h -- voxel coordinate packing + hash shared by rulebook.hip and the host probe.
-// Coordinates: batch < 1023, 0 <= x,y,z < 2^18 (262144 voxels per axis; ScanNet at 2 cm spans
+// Coordinates: batch <= PTC_VOX_BATCH_MAX, 0 <= x,y,z < 2^PTC_VOX_BITS (include/ptcore.h, LIMITS: 262144 voxels per axis; ScanNet at 2 cm spans
 // ~200, nuScenes at 5 cm ~2600).  The all-ones word is reserved as the EMPTY slot marker.
 #pragma once
 #include <stdint.h>
+#include "../../include/ptcore.h"      // PTC_VOX_BITS, PTC_VOX_BATCH_MAX
 #if defined(__HIPCC__)
 #define PTC_HD3 __host__ __device__ __forceinline__
 #else
 #define PTC_HD3 static inline
 #endif
 
-#define PTC_VOX_BITS 18
 #define PTC_VOX_MAX (1 << PTC_VOX_BITS)
-#define PTC_VOX_BATCH_MAX 1023
 #define PTC_HASH_EMPTY 0xffffffffffffffffull
 
 // lexicographic (b, x, y, z) order == numeric order of the packed word

@@ -68,9 +68,10 @@ static inline int wgrad7_slice_cin(int c_in) { return c_in % 64 == 0 ? 64 : 32; 
 static inline int wgrad7_slices(int c_in, int c_out) {
   return wgrad7_sliced(c_in, c_out) ? (c_in / wgrad7_slice_cin(c_in)) * (c_out / 32) : (c_in == 64 ? 2 : 1);
 }
+#define W7_SLICED_MIN_ROWS 1024              // the sliced form; conv7's own shapes: C7_MIN_ROWS
 static inline bool wgrad7_supported(int dtype, int kv, int c_in, int c_out, int bm, int hcap, int64_t n_out) {
   if (conv7_supported(dtype, kv, c_in, c_out, bm, hcap, n_out)) return true;
-  return dtype != PTC_F32 && kv == 27 && bm == C7_BM && hcap == C7_HCAP && n_out >= 1024 && wgrad7_sliced(c_in, c_out) &&
+  return dtype != PTC_F32 && kv == 27 && bm == C7_BM && hcap == C7_HCAP && n_out >= W7_SLICED_MIN_ROWS && wgrad7_sliced(c_in, c_out) &&
          wgrad7_slices(c_in, c_out) <= W7_MAX_WGS;
 }
 // workgroups walking DISTINCT block sequences = fp32 partials per call (C = 64: two workgroups -- the output-channel halves -- per sequence;

@@ -1101,7 +1101,7 @@ def _blk_plan(n, npad, c, heads, x0_f32, dt=torch.bfloat16):
     the slabs, as (table index, offset) lists -- the per-call work is then two allocations and ~45 integer stores per direction"""
     # round 6: where the executor runs the MLP on csrc/mlp.hip (C = 32 | 64) the hidden-width tensors do not exist: no H / ACT / M in the
     # saved slab (2 x N x 4C x 2 bytes per Block: 0.84 GB at N = 819200, C = 64), no DH in the backward's scratch
-    fused = bool(ops.lib().ptc_ptv3_block_mlp_fused(int(c), _lib.PTC_F16 if dt == torch.float16 else _lib.PTC_BF16))
+    fused = ops.block_mlp_fused(c, dt)
     key = (n, npad, c, heads, x0_f32, fused)
     p = _blk_plans.get(key)
     if p is not None:
@@ -1331,7 +1331,7 @@ class _MLP(Function):
         xp = x.to(dt).contiguous()
         w1c, w2c = _cast_cache.get(w1, dt).contiguous(), _cast_cache.get(w2, dt).contiguous()
         ctx.dtypes = (x.dtype, w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
-        ctx.one_kernel = config.MLP_ONE_KERNEL and w1.shape[0] == 4 * w1.shape[1] and w2.shape[0] == w1.shape[1] and ops.mlp_supported(w1.shape[1], dt)
+        ctx.one_kernel = w1.shape[0] == 4 * w1.shape[1] and w2.shape[0] == w1.shape[1] and ops.block_mlp_fused(w1.shape[1], dt)
         if ctx.one_kernel:      # round 6 (csrc/mlp.hip): the hidden tensor never reaches memory, the backward recomputes it; same bits as below
             ctx.save_for_backward(xp, w1c, w2c, b1)
             return ops.mlp_fwd(xp, w1c, b1, w2c, b2)
@@ -1528,7 +1528,7 @@ def pg_ball_query_torch(xyz: torch.Tensor, batch_idxs: torch.Tensor, batch_offse
             d2 = dx * dx + dy * dy
             d2 = d2 + dz * dz
             hit = d2 < r2
-            hit &= torch.cumsum(hit.to(torch.int32), dim=1) <= 1000
+            hit &= torch.cumsum(hit.to(torch.int32), dim=1) <= ops.PG_MAX_NEIGHBOURS
             lens[rows] = hit.sum(1)
             rr, kk = torch.nonzero(hit, as_tuple=True)
             pieces.append((rows[rr], kk + s))

@@ -15,6 +15,21 @@ from . import _lib
 from ._lib import PtcoreError, check, dtype_code, lib, ptr, require_cuda, stream_ptr  # noqa: F401  (check: for callers of lib(checked=False))
 
 _DT = _lib.DTYPE_CODES      # torch dtype -> ptc_dtype tag
+# Limits and code sets are READ from the C-ABI headers (_lib parsed them: no library load); shape rules are ASKED of the library (_ask).
+_K, _KA = _lib.HEADER.constants, _lib.AUGMENT_HEADER.constants
+ATTN_HEAD_DIM = _K["PTC_ATTN_HEAD_DIM"]      # the base attention kernels, their dropout form and the RPE form (other head dims: attention_hd.h)
+EDGE_ROWS_GROUP, EDGE_ROWS_SUB, EDGE_ROWS_REL = (_K["PTC_EDGE_ROWS_" + k] for k in ("GROUP", "SUB", "REL"))     # `mode` of the edge_* ops
+EDGE_REDUCE_INTERP, EDGE_REDUCE_AGG, EDGE_REDUCE_POS = (_K["PTC_EDGE_REDUCE_" + k] for k in ("INTERP", "AGG", "POS"))
+EDGE_SCATTER_GROUP, EDGE_SCATTER_SUB, EDGE_SCATTER_INTERP, EDGE_SCATTER_AGG = (_K["PTC_EDGE_SCATTER_" + k] for k in ("GROUP", "SUB", "INTERP", "AGG"))
+_asked: dict = {}           # (entry point, *scalars) -> its answer
+
+
+def _ask(name: str, *args):      # a scalar-only predicate / query of the library, asked once per argument tuple
+    key = (name,) + args
+    r = _asked.get(key)
+    if r is None:
+        r = _asked[key] = getattr(lib(), name)(*args)
+    return r
 
 
 def _ws(nbytes: int, device) -> torch.Tensor:
@@ -264,7 +279,7 @@ def _edge_idx(idx: torch.Tensor):
 
 
 def edge_rows(mode: int, src, a, idx, out=None, out_col0: int = 0):
-    """Per-edge rows (mode 0 src[j], 1 a[t] - src[j], 2 src[j] - a[t] with zeros for empty slots) -> out [m, nsample, c], or written
+    """Per-edge rows (GROUP src[j], SUB a[t] - src[j], REL src[j] - a[t] with zeros for empty slots) -> out [m, nsample, c], or written
     into the column window [out_col0, out_col0 + c) of a caller's wider `out` [m, nsample, width]."""
     require_cuda(src, a, idx, out)
     src, idx = _f32_rows(src, "src"), _edge_idx(idx)
@@ -281,7 +296,7 @@ def edge_rows(mode: int, src, a, idx, out=None, out_col0: int = 0):
 
 
 def edge_reduce(mode: int, src, pos, w, idx, m: int, nsample: int, c: int, w_c: int = 1, pos_stride: int = 0, pos_col0: int = 0):
-    """Per-target sums over the nsample edges of a row -> [m, c] (mode 0 interpolation, 1 aggregation, 2 plain row sums of `pos`)."""
+    """Per-target sums over the nsample edges of a row -> [m, c] (INTERP interpolation, AGG aggregation, POS plain row sums of `pos`)."""
     require_cuda(src, pos, w, idx)
     out = torch.empty((m, c), dtype=torch.float32, device=(pos if src is None else src).device)
     n_src = 0 if src is None else src.shape[0]
@@ -396,7 +411,7 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor, idx2: Optional[torch.Tenso
 
 def gather_rows_add_supported(src: torch.Tensor, addend: torch.Tensor) -> bool:
     return (src.dim() == 2 and addend.dim() == 2 and src.dtype == addend.dtype and src.shape[1] == addend.shape[1]
-            and src.dtype in (torch.float32, torch.bfloat16, torch.float16) and src.shape[1] % (4 if src.dtype == torch.float32 else 8) == 0)
+            and src.dtype in _DT and bool(_ask("ptc_gather_rows_add_supported", int(src.shape[1]), _DT[src.dtype])))
 
 
 def gather_rows_add(src: torch.Tensor, idx: torch.Tensor, addend: torch.Tensor) -> torch.Tensor:
@@ -443,12 +458,12 @@ def segment_csr_bwd(grad_out: torch.Tensor, perm: Optional[torch.Tensor], indptr
 # ------------------------------------------------------------------------------------------------
 # rulebooks
 # ------------------------------------------------------------------------------------------------
-VOX_MAX = 1 << 18
-BATCH_MAX = 1023
+VOX_MAX = 1 << _K["PTC_VOX_BITS"]
+BATCH_MAX = _K["PTC_VOX_BATCH_MAX"]
 
 
 def check_coord_range(coord_max_host, batch_size: int, spatial_shape=None) -> None:
-    """The voxel hash packs (batch, x, y, z) into 10 + 3 x 18 bits (csrc/voxel_hash.h): coordinates outside [0, 2^18) --
+    """The voxel hash packs (batch, x, y, z) into 10 + 3 x PTC_VOX_BITS bits (csrc/voxel_hash.h): coordinates outside [0, VOX_MAX) --
     ptc_coord_max reports a negative coordinate as a negative maximum -- or outside the declared spatial_shape, or more
     than BATCH_MAX batch items, would alias other voxels' keys and give silently wrong neighbour maps.  Host integers
     only (they ride in the one host sync of the forward): no device work."""
@@ -487,7 +502,7 @@ def rulebook_subm(indices: torch.Tensor, ksize: int, table: Optional[HashTable] 
     return nbr
 
 
-BLOCK_BM, BLOCK_HCAP = 128, 416     # = C7_BM, C7_HCAP of csrc/conv7.h
+BLOCK_BM, BLOCK_HCAP = _K["PTC_BLOCK_BM"], _K["PTC_BLOCK_HCAP"]
 
 
 class BlockTables:
@@ -514,19 +529,14 @@ class BlockTables:
 
 
 def block_plan(c_in: int, c_out: int, kv: int, dtype: torch.dtype, n_rows: int = 1 << 30):
-    """(bm, hcap) of the block-local tables for this shape, or None when the shape stays on the global-gather kernels.  Two consumers:
-    the LDS-staged, register-weight convolution (csrc/conv7.h conv7_supported: 16-bit, 3^3 table, c_in = c_out in {32, 64}, >= 4096
-    rows) and the accumulator-stationary weight gradient (csrc/wgrad7.h: the same shapes, plus -- round 4 -- every c_in % 32 == 0,
-    c_out % 32 == 0 shape (the 128 .. 512-channel stages, SpUNet's 96-channel decoder) as (32 x 64 | 32)-channel slices; the forward of those shapes takes the tables and
-    falls back to the global-gather kernel inside ptc_spconv_fwd_blk)."""
-    if dtype == torch.float32 or kv != 27:
-        return None
-    if c_in == c_out and c_in in (32, 64):
-        return (BLOCK_BM, BLOCK_HCAP) if n_rows >= 4096 else None
-    if c_in % 32 == 0 and c_out % 32 == 0 and c_in <= 1024 and c_out <= 1024 and (c_in // (64 if c_in % 64 == 0 else 32)) * (c_out // 32) <= 256 \
-            and n_rows >= 1024:
-        return (BLOCK_BM, BLOCK_HCAP)
-    return None
+    """(bm, hcap) of the block-local tables for this shape, or None when it stays on the global-gather kernels: what the weight gradient
+    takes (wgrad7_supported, csrc/wgrad7.h: conv7's shapes and the sliced wider ones; conv7 / conv8 take a subset: BlockProvider.get)."""
+    return (BLOCK_BM, BLOCK_HCAP) if _blk_takes("PTC_CONSUMER_WGRAD7", c_in, c_out, kv, dtype, n_rows) else None
+
+
+def _blk_takes(consumer: str, c_in: int, c_out: int, kv: int, dtype: torch.dtype, n_rows: int) -> bool:
+    """whether `consumer` (enum ptc_blk_consumer) takes such tables of n_rows rows: the launch paths' predicates, asked once per shape"""
+    return dtype in _DT and 0 <= _ask("ptc_spconv_blk_min_rows", _K[consumer], int(kv), int(c_in), int(c_out), _DT[dtype]) <= n_rows
 
 
 class BlockProvider:
@@ -537,14 +547,15 @@ class BlockProvider:
         self.tables = {}
 
     def get(self, c_in: int, c_out: int, dtype: torch.dtype, conv: bool = False):
-        """conv=True: asked by a forward / input-gradient convolution -- only the shapes conv7 serves (c_in = c_out in {32, 64}) get
-        tables there; the sliced weight gradient of the wider shapes asks with conv=False from the backward, so inference, eval and
-        PTC_WGRAD_BLK=0 never pay the table build (one launch + ~112 B per row) for a kernel that cannot use it."""
-        plan = block_plan(c_in, c_out, self.nbr.shape[0], dtype, self.nbr.shape[1])
-        from . import config
-
-        conv_kernel = (c_in == c_out and c_in in (32, 64)) or (config.CONV8 and c_in >= 96)      # conv7 | conv8 (round 6: c_in % 32 == 0 from 96 up)
-        if plan is None or not self.nbr.is_cuda or (conv and not conv_kernel):
+        """conv=True: asked by a forward / input-gradient convolution -- only the shapes conv7 or conv8 would take (the library's answer,
+        PTC_CONV8 included) get tables there; the sliced weight gradient of the other shapes asks with conv=False from the backward, so
+        inference, eval and PTC_WGRAD_BLK=0 never pay the table build (one launch + ~112 B per row) for a kernel that cannot use it."""
+        if not self.nbr.is_cuda:
+            return None
+        kv, n = self.nbr.shape
+        plan = block_plan(c_in, c_out, kv, dtype, n)
+        if plan is None or (conv and not (_blk_takes("PTC_CONSUMER_CONV7", c_in, c_out, kv, dtype, n)
+                                          or _blk_takes("PTC_CONSUMER_CONV8", c_in, c_out, kv, dtype, n))):
             return None
         t = self.tables.get(plan)
         if t is None:
@@ -576,9 +587,6 @@ def rulebook_down(indices: torch.Tensor, coord_bits: int, batch_bits: int):
 # ------------------------------------------------------------------------------------------------
 # sparse conv compute
 # ------------------------------------------------------------------------------------------------
-_fwd_blk_ws: dict = {}      # (kv, c_in, c_out) -> ptc_spconv_fwd_blk_workspace_bytes
-
-
 def spconv_fwd(feat: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                nbr: Optional[torch.Tensor], blk: Optional["BlockTables"] = None) -> torch.Tensor:
     """out[o] = bias + sum_k W[:,k,:] . feat[nbr[k][o]].  weight [C_out, kv, C_in] in feat.dtype,
@@ -606,9 +614,7 @@ def spconv_fwd(feat: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     if blk is not None and nbr is not None:
         if blk.nbr.data_ptr() != nbr.data_ptr() or tuple(blk.nbr.shape) != tuple(nbr.shape):
             raise PtcoreError("blk was built from another gather table")
-        nbytes = _fwd_blk_ws.get((kv, c_in, c_out))       # the wide kernel's fragment-ordered weights; a function of the shape alone
-        if nbytes is None:
-            nbytes = _fwd_blk_ws[(kv, c_in, c_out)] = int(lib().ptc_spconv_fwd_blk_workspace_bytes(n_out, kv, c_in, c_out))
+        nbytes = _ask("ptc_spconv_fwd_blk_workspace_bytes", 0, kv, c_in, c_out)       # the wide kernel's fragment-ordered weights; n_out is ignored
         ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device) if nbytes else None
         lib().ptc_spconv_fwd_blk(ptr(feat), feat.shape[0], ptr(weight), ptr(bias), ptr(nbr), ptr(blk.tab), ptr(blk.hid),
                                  ptr(blk.hcnt), blk.bm, blk.hcap, n_out, kv, c_in, c_out, dtype_code(feat), ptr(out),
@@ -799,7 +805,7 @@ def add_norm_fwd(u, a, row_scale, norm_a, norm_b, y_dtype):
 
 
 def linear_joint_supported(c_in: int, c_out: int, dtype: torch.dtype) -> bool:
-    return dtype in (torch.bfloat16, torch.float16) and bool(lib().ptc_linear_joint_supported(int(c_in), int(c_out), _DT[dtype]))
+    return dtype in _DT and bool(lib().ptc_linear_joint_supported(int(c_in), int(c_out), _DT[dtype]))
 
 
 def linear_joint_fwd(x, weight, bias, table, a, row_scale, norm_b, y_dtype, n_out=None):
@@ -875,11 +881,8 @@ def add_norm_bwd(dz_in, dy, z, u, row_scale, g_a, st_a, g_b, st_b, want_affine_a
 # attention
 # ------------------------------------------------------------------------------------------------
 def attn_hd_supported(head_dim: int, max_seqlen: int) -> bool:
-    """True when (head_dim, max_seqlen) is served by the MFMA window-attention kernels: head_dim 16 up to 1024 keys,
-    17..32 up to 1024, ..48 up to 672, ..64 up to 512 (the window's operands stay in LDS)."""
-    if head_dim == 16:
-        return 1 <= int(max_seqlen) <= 1024
-    return bool(lib().ptc_attn_varlen_hd_supported(int(head_dim), int(max_seqlen)))
+    """True when the window-attention kernels serve (head_dim, max_seqlen): head_dim 16 .. 64, max_seqlen bounded by LDS (ptcore.h, H)."""
+    return bool(_ask("ptc_attn_varlen_hd_supported", int(head_dim), int(max_seqlen)))
 
 
 def attn_varlen_fwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int, softmax_scale: float, dropout_p: float = 0.0, seed: int = 0):
@@ -896,11 +899,11 @@ def attn_varlen_fwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int
     out = torch.empty((T, H, D), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((H, T), dtype=torch.float32, device=qkv.device)
     if dropout_p > 0.0:       # attention dropout (csrc/attention_drop.h): head_dim 16; the mask is a function of `seed`, regenerated by the backward
-        if D != 16:
-            raise PtcoreError("attention dropout is implemented for head_dim 16")
+        if D != ATTN_HEAD_DIM:
+            raise PtcoreError(f"attention dropout is implemented for head_dim {ATTN_HEAD_DIM}")
         lib().ptc_attn_varlen_dropout_fwd(ptr(qkv), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen), float(softmax_scale), dtype_code(qkv),
                                           float(dropout_p), int(seed), ptr(out), ptr(lse), stream_ptr())
-    elif D == 16:
+    elif D == ATTN_HEAD_DIM:
         lib().ptc_attn_varlen_fwd(ptr(qkv), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen), float(softmax_scale),
                                   dtype_code(qkv), ptr(out), ptr(lse), stream_ptr())
     else:
@@ -923,7 +926,7 @@ def attn_varlen_bwd(qkv, out, dout, lse, cu_seqlens, max_seqlen: int, softmax_sc
         lib().ptc_attn_varlen_dropout_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), cu.numel() - 1, T, H, int(max_seqlen),
                                           float(softmax_scale), dtype_code(qkv), float(dropout_p), int(seed), ptr(dqkv), ptr(ws), nbytes,
                                           stream_ptr())
-    elif D == 16:
+    elif D == ATTN_HEAD_DIM:
         lib().ptc_attn_varlen_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(cu), cu.numel() - 1, T, H,
                                   int(max_seqlen), float(softmax_scale), dtype_code(qkv), ptr(dqkv), ptr(ws), nbytes,
                                   stream_ptr())
@@ -974,18 +977,8 @@ def attn_rope_bwd(qkv, out, dout, lse, xyz, inv_freq, cu_seqlens, max_seqlen: in
 
 
 def attn_rpe_supported(head_dim: int, max_seqlen: int, pos_bnd: int, dtype: torch.dtype = torch.bfloat16) -> bool:
-    """RPE attention kernels: head_dim 16, windows whose images + coordinates + table fit LDS -- the 16-bit budget of attention_rpe.h for
-    bf16 / f16, the fp32 one of attention_rpe_f32.h (two fp32 window images, lse / delta, coordinates, table) for torch.float32."""
-    lp = (int(max_seqlen) + 31) & ~31
-    r = 2 * int(pos_bnd) + 1
-    t4 = (3 * r + 3) & ~3
-    if dtype == torch.float32:
-        fits = max(lp * 136 + t4 * 12 + 32, lp * 144 + t4 * 4) <= 163840
-    elif dtype in (torch.bfloat16, torch.float16):
-        fits = lp * 72 + lp * 8 + t4 * 8 <= 163840
-    else:
-        return False
-    return head_dim == 16 and 1 <= max_seqlen <= 1024 and pos_bnd >= 0 and fits
+    """RPE attention kernels: head_dim 16, window images + coordinates + table within the LDS budget of forward and backward"""
+    return dtype in _DT and bool(_ask("ptc_attn_rpe_supported", int(head_dim), int(max_seqlen), int(pos_bnd), _DT[dtype]))
 
 
 def attn_rpe_fwd(qkv, cu_seqlens, max_seqlen: int, softmax_scale: float, grid_coord, rpe_table, pos_bnd: int):
@@ -993,8 +986,8 @@ def attn_rpe_fwd(qkv, cu_seqlens, max_seqlen: int, softmax_scale: float, grid_co
     lse [H,T] fp32).  f16 tensors (the reference's fp16 AMP) ride around the same bf16 arithmetic: the casts sit in the kernels' load /
     store paths.  fp32 tensors (no autocast) run the fp32 kernels: fp32 operands, logits, softmax and accumulation."""
     require_cuda(qkv, cu_seqlens, grid_coord, rpe_table)
-    if qkv.dtype not in (torch.bfloat16, torch.float16, torch.float32) or qkv.dim() != 4 or qkv.shape[1] != 3 or qkv.shape[3] != 16:
-        raise PtcoreError(f"qkv must be bf16 / f16 / fp32 [T,3,H,16], got {qkv.dtype} {tuple(qkv.shape)}")
+    if qkv.dtype not in (torch.bfloat16, torch.float16, torch.float32) or qkv.dim() != 4 or qkv.shape[1] != 3 or qkv.shape[3] != ATTN_HEAD_DIM:
+        raise PtcoreError(f"qkv must be bf16 / f16 / fp32 [T,3,H,{ATTN_HEAD_DIM}], got {qkv.dtype} {tuple(qkv.shape)}")
     T, _, H, _ = qkv.shape
     if grid_coord.dtype != torch.int32 or tuple(grid_coord.shape) != (T, 3):
         raise PtcoreError(f"grid_coord must be int32 [{T},3], got {grid_coord.dtype} {tuple(grid_coord.shape)}")
@@ -1080,9 +1073,9 @@ def cross_entropy_bwd(logits: torch.Tensor, target: torch.Tensor, lse: torch.Ten
     return out
 
 
-CRITERIA_ROWS_MAX_C = 32        # csrc/loss_rows.h LR_CP: the register-row path serves every term
-CRITERIA_CE_MAX_C = 1024        # wider rows: the cross-entropy term alone, element-wise
-CRITERIA_CE, CRITERIA_FOCAL, CRITERIA_DICE = 1, 2, 4
+CRITERIA_ROWS_MAX_C = _K["PTC_CRITERIA_ROWS_MAX_C"]     # the register-row path (csrc/loss_rows.h) serves every term
+CRITERIA_CE_MAX_C = _K["PTC_CRITERIA_CE_MAX_C"]         # wider rows: the cross-entropy term alone, element-wise
+CRITERIA_CE, CRITERIA_FOCAL, CRITERIA_DICE = (_K[k] for k in ("PTC_CRITERIA_CE", "PTC_CRITERIA_FOCAL", "PTC_CRITERIA_DICE"))
 
 
 class CriteriaSpec:
@@ -1100,10 +1093,7 @@ class CriteriaSpec:
 
 
 def _criteria_check(spec: CriteriaSpec, lg: torch.Tensor):
-    c = lg.shape[1]
-    if spec.flags == 0 or c > CRITERIA_CE_MAX_C or (c > CRITERIA_ROWS_MAX_C and spec.flags != CRITERIA_CE):
-        raise PtcoreError(f"criteria kernels: terms {spec.flags} over {c} classes (every term up to {CRITERIA_ROWS_MAX_C}, cross entropy "
-                          f"alone up to {CRITERIA_CE_MAX_C})")
+    c = lg.shape[1]      # (the class limits CRITERIA_ROWS_MAX_C / CRITERIA_CE_MAX_C are the library's to refuse)
     for name, vec in (("weight", spec.ce_weight), ("alpha", spec.focal_alpha_vec)):
         if vec is not None and (vec.dtype != torch.float32 or vec.numel() != c or vec.device != lg.device or not vec.is_contiguous()):
             raise PtcoreError(f"criteria kernels: {name} must be a contiguous fp32 [{c}] tensor on the logits' device")
@@ -1149,8 +1139,8 @@ def criteria_rows_bwd(logits: torch.Tensor, target: torch.Tensor, lse: torch.Ten
     return out
 
 
-LOVASZ_DENSE_MAX_C = 64         # csrc/lovasz.hip LV_MAX_C: the dense [C, N] path
-LOVASZ_MAX_C = 1024             # LW_MAX_C: the row-compacted path
+LOVASZ_DENSE_MAX_C = _K["PTC_LOVASZ_DENSE_MAX_C"]       # the dense [C, N] path (csrc/lovasz.hip LV_MAX_C)
+LOVASZ_MAX_C = _K["PTC_LOVASZ_MAX_C"]                   # the row-compacted path (LW_MAX_C)
 
 
 class LovaszPresent:
@@ -1190,8 +1180,6 @@ def lovasz_present(target: torch.Tensor, num_classes: int, ignore_index: int) ->
     if target.dtype != torch.int64 or target.dim() != 1:
         raise PtcoreError("target must be int64 [N]")
     c = int(num_classes)
-    if not 1 <= c <= LOVASZ_MAX_C:
-        raise PtcoreError(f"lovasz_present: {c} classes (1 .. {LOVASZ_MAX_C} are served)")
     tg = target.contiguous()
     buf = torch.empty(3 * c + 1, dtype=torch.int32, device=tg.device)
     count, row_of, class_of, n_present = buf[:c], buf[c:2 * c], buf[2 * c:3 * c], buf[3 * c:]
@@ -1218,9 +1206,7 @@ def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, ignore_index: int
         raise PtcoreError("target must be int64")
     lg, rs = _rows_view(logits)
     n, c = lg.shape
-    if present is None and c > LOVASZ_DENSE_MAX_C:
-        if c > LOVASZ_MAX_C:
-            raise PtcoreError(f"lovasz_softmax: unsupported shape [{n}, {c}] (at most {LOVASZ_MAX_C} classes)")
+    if present is None and c > LOVASZ_DENSE_MAX_C:       # (past LOVASZ_MAX_C the library refuses)
         present = lovasz_present(target, c, ignore_index)
     if present is not None:
         return _lovasz_softmax_rows(lg, rs, target, ignore_index, present)
@@ -1239,8 +1225,6 @@ def _lovasz_softmax_rows(lg, rs, target, ignore_index, present):
     n, c = lg.shape
     if not isinstance(present, LovaszPresent):
         raise PtcoreError("lovasz_softmax: `present` must come from lovasz_present")
-    if c > LOVASZ_MAX_C or c < 1:
-        raise PtcoreError(f"lovasz_softmax: unsupported shape [{n}, {c}] (at most {LOVASZ_MAX_C} classes)")
     if target.dim() != 1 or target.shape[0] != n:
         raise PtcoreError("lovasz_softmax: target must be [N]")
     if not present.matches(target, c, ignore_index):
@@ -1262,13 +1246,11 @@ def _lovasz_softmax_rows(lg, rs, target, ignore_index, present):
 # ------------------------------------------------------------------------------------------------
 # BatchNorm1d + activation
 # ------------------------------------------------------------------------------------------------
-ACT_CODES = {"none": 0, "gelu": 1, "relu": 2}
+ACT_CODES = {k[len("PTC_ACT_"):].lower(): v for k, v in _lib.HEADER.enums["ptc_act"].items()}       # "none": 0, ...
 
 
 def batch_norm_supported(c: int, dtype: torch.dtype) -> bool:
-    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    return bool(lib().ptc_batch_norm_supported(int(c), _DT[dtype]))
+    return dtype in _DT and bool(lib().ptc_batch_norm_supported(int(c), _DT[dtype]))
 
 
 def batch_norm_act_fwd(x, gamma, beta, running_mean, running_var, training: bool, momentum: float, eps: float, act: str,
@@ -1345,9 +1327,7 @@ def column_sum(x: torch.Tensor) -> torch.Tensor:
 
 
 def linear_supported_ex(c_in: int, c_out: int, dtype: torch.dtype) -> bool:
-    if dtype not in (torch.bfloat16, torch.float16):
-        return False
-    return bool(lib().ptc_linear_supported_ex(int(c_in), int(c_out), _DT[dtype]))
+    return dtype in _DT and bool(lib().ptc_linear_supported_ex(int(c_in), int(c_out), _DT[dtype]))
 
 
 def linear_gelu_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]):
@@ -1376,9 +1356,12 @@ def linear_gelu_bwd_input(g: torch.Tensor, weight_t: torch.Tensor, h: torch.Tens
 
 def mlp_supported(c: int, dtype: torch.dtype) -> bool:
     """the one-kernel MLP (csrc/mlp.hip): C = 32 | 64 (hidden 4 C), bf16 / f16"""
-    if dtype not in (torch.bfloat16, torch.float16):
-        return False
-    return bool(lib().ptc_mlp_supported(int(c), _DT[dtype]))
+    return dtype in _DT and bool(lib().ptc_mlp_supported(int(c), _DT[dtype]))
+
+
+def block_mlp_fused(c: int, dtype: torch.dtype) -> bool:
+    """mlp_supported and not PTC_BLK_MLP_FUSED=0, which the library alone reads: the block executor's answer, for the Python path too"""
+    return dtype in _DT and bool(_ask("ptc_ptv3_block_mlp_fused", int(c), _DT[dtype]))
 
 
 def mlp_fwd(x, w1, b1, w2, b2, a=None, row_scale=None, want_y=True):
@@ -1646,7 +1629,7 @@ def cluster_agg_bwd(us, vs, a, dout: torch.Tensor, state: torch.Tensor, gc: Grid
 # ------------------------------------------------------------------------------------------------
 # PointGroup clustering and heads (csrc/pg_cluster.hip)
 # ------------------------------------------------------------------------------------------------
-PG_MAX_NEIGHBOURS = 1000
+PG_MAX_NEIGHBOURS = _K["PTC_PG_MAX_NEIGHBOURS"]
 
 
 def pg_ball_query(xyz: torch.Tensor, batch_idxs: torch.Tensor, n_batch: int, radius: float):
@@ -1767,7 +1750,7 @@ def pg_bias_loss_bwd(bias_pred, coord, centroid, instance, ignore_index: int, do
 # ------------------------------------------------------------------------------------------------
 # Masked Scene Contrast (csrc/msc.hip)
 # ------------------------------------------------------------------------------------------------
-MSC_MAX_K = 8
+MSC_MAX_K = _K["PTC_MSC_MAX_K"]
 
 
 def _msc_offsets(offset, new_offset, what):
@@ -1785,8 +1768,6 @@ def msc_match(k: int, max_radius: float, xyz, offset, new_xyz, new_offset):
     require_cuda(xyz, offset, new_xyz, new_offset)
     x, q = _xyz(xyz, "xyz"), _xyz(new_xyz, "new_xyz")
     off, noff = _msc_offsets(offset, new_offset, "msc_match")
-    if not 1 <= int(k) <= MSC_MAX_K:
-        raise PtcoreError(f"msc_match: k={k} not in [1, {MSC_MAX_K}]")
     n, m, dev = x.shape[0], q.shape[0], q.device
     count = torch.empty(m, dtype=torch.int32, device=dev)
     cand = torch.empty((m, int(k)), dtype=torch.int32, device=dev)
@@ -1868,8 +1849,6 @@ def _msc_nce_args(feat1, feat2, match_index):
     if feat1.dtype != torch.float32 or feat2.dtype != torch.float32 or feat1.dim() != 2 or feat2.dim() != 2 or feat1.shape[1] != feat2.shape[1]:
         raise PtcoreError("msc_nce: feat1 / feat2 must be fp32 [N, C] with equal C")
     c = feat1.shape[1]
-    if c % 4 or not 4 <= c <= 256:
-        raise PtcoreError(f"msc_nce: C={c} is not a multiple of 4 in [4, 256]")
     mi = match_index.to(torch.int64).contiguous()
     if mi.dim() != 2 or mi.shape[1] != 2 or mi.shape[0] < 1:
         raise PtcoreError("msc_nce: match_index must be [P, 2] with P >= 1")
@@ -1911,8 +1890,6 @@ def _msc_csc_nce_args(feat1, coord1, offset1, feat2, coord2, match_index, r1, r2
     if feat1.dtype != torch.float32 or feat2.dtype != torch.float32 or feat1.dim() != 2 or feat2.dim() != 2 or feat1.shape[1] != feat2.shape[1]:
         raise PtcoreError("msc_csc_nce: feat1 / feat2 must be fp32 [N, C] with equal C")
     c = feat1.shape[1]
-    if c % 4 or not 4 <= c <= 256:
-        raise PtcoreError(f"msc_csc_nce: C={c} is not a multiple of 4 in [4, 256]")
     mi = match_index.to(torch.int64).contiguous()
     if mi.dim() != 2 or mi.shape[1] != 2 or mi.shape[0] < 1:
         raise PtcoreError("msc_csc_nce: match_index must be [P, 2] with P >= 1")
@@ -2094,9 +2071,7 @@ def cac_distill_bwd(state, smoothness: float, eps: float, stats, dloss):
 # Point Prompt Training's language-guided head (csrc/ppt.hip)
 # ------------------------------------------------------------------------------------------------
 def ppt_head_supported(c: int, d: int, k: int, dtype: torch.dtype) -> bool:
-    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    return bool(lib().ptc_ppt_head_supported(int(c), int(d), int(k), _DT[dtype]))
+    return dtype in _DT and bool(lib().ptc_ppt_head_supported(int(c), int(d), int(k), _DT[dtype]))
 
 
 def _ppt_f32(t: torch.Tensor, shape, what: str, dtype=torch.float32) -> torch.Tensor:
@@ -2284,7 +2259,7 @@ def sgi_targets(instance, segment, sp_inverse, offset, lk: Sequence[int], g: Seq
 # Sonata-v1m1 distillation loss (csrc/sonata.hip): Sinkhorn-Knopp in scaling-vector form and the fused soft cross entropy
 # ------------------------------------------------------------------------------------------------
 def sonata_supported(k: int) -> bool:
-    """the kernels take K prototypes, a multiple of 64 up to 8192"""
+    """whether the kernels take K prototypes (ptc_sonata_supported states the rule: include/ptcore.h)"""
     return bool(lib().ptc_sonata_supported(int(k)))
 
 
@@ -2293,7 +2268,7 @@ def _sonata_rows(x, what):
     if x.dim() != 2 or x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise PtcoreError(f"{what}: logits must be [N, K] in fp32, fp16 or bf16, got {tuple(x.shape)} {x.dtype}")
     if not sonata_supported(x.shape[1]):
-        raise PtcoreError(f"{what}: K={x.shape[1]} is not a multiple of 64 in [64, 8192]")
+        raise PtcoreError(f"{what}: K={x.shape[1]} prototypes are not served (ptc_sonata_supported, include/ptcore.h)")
     return x.detach().contiguous()
 
 
@@ -2406,7 +2381,7 @@ def sonata_patch_rank(grid_coord: torch.Tensor, batch: torch.Tensor, n_batch: in
 # ------------------------------------------------------------------------------------------------
 # Concerto-v1m1 2D-3D alignment branch (csrc/concerto.hip)
 # ------------------------------------------------------------------------------------------------
-_CONCERTO_CORR_TYPES = {torch.float32: 0, torch.int32: 1, torch.int64: 2}
+_CONCERTO_CORR_TYPES = {torch.float32: _K["PTC_CORR_F32"], torch.int32: _K["PTC_CORR_I32"], torch.int64: _K["PTC_CORR_I64"]}
 
 
 def concerto_pool_corr(corr: torch.Tensor, perm: Optional[torch.Tensor], idx_ptr: torch.Tensor) -> torch.Tensor:
@@ -2537,9 +2512,10 @@ def concerto_align(feature2d: torch.Tensor, patch_ids: torch.Tensor, y: torch.Te
 # ------------------------------------------------------------------------------------------------
 # device-side point augmentation (csrc/augment.hip)
 # ------------------------------------------------------------------------------------------------
-AUG_CENTER_SHIFT, AUG_ROTATE, AUG_SCALE, AUG_FLIP, AUG_SHIFT = range(5)                 # ptc_aug_compose descriptor kinds
-AUG_C_AUTOCONTRAST, AUG_C_TRANSLATION, AUG_C_JITTER, AUG_C_NORMALIZE = range(4)          # ptc_aug_apply colour op kinds
-AUG_MAX_OPS, AUG_MAX_COLOR_OPS = 16, 8
+# csrc/ptcore_augment.h: ptc_aug_compose descriptor kinds, ptc_aug_apply colour op kinds, and the per-call limits of both
+AUG_CENTER_SHIFT, AUG_ROTATE, AUG_SCALE, AUG_FLIP, AUG_SHIFT = (_KA["PTC_AUG_" + k] for k in ("CENTER_SHIFT", "ROTATE", "SCALE", "FLIP", "SHIFT"))
+AUG_C_AUTOCONTRAST, AUG_C_TRANSLATION, AUG_C_JITTER, AUG_C_NORMALIZE = (_KA["PTC_AUG_C_" + k] for k in ("AUTOCONTRAST", "TRANSLATION", "JITTER", "NORMALIZE"))
+AUG_MAX_OPS, AUG_MAX_COLOR_OPS = _KA["PTC_AUG_MAX_OPS"], _KA["PTC_AUG_MAX_COLOR_OPS"]
 AUG_STREAM_JITTER, AUG_STREAM_COLOR, AUG_STREAM_ELASTIC = 0, 1, 2                        # generator streams (elastic stage s: 2 + s)
 
 
@@ -2602,8 +2578,6 @@ def aug_apply(coord=None, normal=None, color=None, aff=None, stats=None, jitter=
         raise PtcoreError("aug_apply: nothing to write")
     n, device = ref.shape[0], ref.device
     color_ops = list(color_ops)
-    if len(color_ops) > AUG_MAX_COLOR_OPS:
-        raise PtcoreError(f"aug_apply: {len(color_ops)} colour ops (at most {AUG_MAX_COLOR_OPS} per flush)")
     k = len(color_ops)
     flat = (ctypes.c_double * max(6 * k, 1))()
     noise_ptrs = (ctypes.c_void_p * max(k, 1))()

@@ -212,8 +212,8 @@ class SerializedAttention(PointModule):
             assert upcast_softmax is False, "Set upcast_softmax to False when enable Flash Attention"
             if not 16 <= channels // num_heads <= 64:
                 raise PtcoreError(f"engine flash attention needs 16 <= head_dim <= 64, got {channels // num_heads}")
-            if attn_drop != 0.0 and channels // num_heads != 16:      # csrc/attention_drop.h: head_dim 16 (every PT-v3m1 / m2 stage)
-                raise PtcoreError("attention dropout in the flash branch is implemented for head_dim 16 (every reference config uses 0.0)")
+            if attn_drop != 0.0 and channels // num_heads != ops.ATTN_HEAD_DIM:      # csrc/attention_drop.h (every PT-v3m1 / m2 stage)
+                raise PtcoreError(f"attention dropout in the flash branch is implemented for head_dim {ops.ATTN_HEAD_DIM} (every reference config uses 0.0)")
             self.patch_size = patch_size
             self.attn_drop = attn_drop
         else:
@@ -228,8 +228,7 @@ class SerializedAttention(PointModule):
     def _kernel_ok(self) -> bool:
         drop = self.attn_drop.p if isinstance(self.attn_drop, nn.Dropout) else self.attn_drop
         hd = self.channels // self.num_heads
-        fits = self.patch_size <= (1024 if hd <= 32 else 672 if hd <= 48 else 512)       # ops.attn_hd_supported, host-side
-        return self.rpe is None and 16 <= hd <= 64 and fits and (drop == 0.0 or not self.training)
+        return self.rpe is None and ops.attn_hd_supported(hd, self.patch_size) and (drop == 0.0 or not self.training)
 
     @torch.no_grad()
     def get_rel_pos(self, point, order):
@@ -354,7 +353,7 @@ class SerializedAttention(PointModule):
             # through the inverse table (ptv3m1:216,219).  Two full gather passes less per block.
             qkv_s = self.qkv(point.feat, tabs[0], tabs[1])
             drop = float(self.attn_drop) if (self.enable_flash and self.training) else 0.0        # ptv3m1:212
-            if qkv_s.dtype == torch.float16 and C // H == 16:
+            if qkv_s.dtype == torch.float16 and C // H == ops.ATTN_HEAD_DIM:
                 # fp16 autocast: qkv.to(bfloat16) and feat.to(qkv.dtype) (ptv3m1:209,215) happen inside the kernels' loads and stores
                 out = PF.attn_varlen_qkvpacked(qkv_s.reshape(-1, 3, H, C // H), cu_seqlens, K, self.scale, drop)
                 feat = self.proj(out.reshape(-1, C), tabs[2], tabs[3])

@@ -51,11 +51,11 @@ class _EdgeGather(torch.autograd.Function):
         c = feat.shape[1]
         f32 = feat.float()
         if xyz is None:
-            out = ops.edge_rows(0, f32, None, idx)
+            out = ops.edge_rows(ops.EDGE_ROWS_GROUP, f32, None, idx)
         else:
             out = torch.empty((m, ns, 3 + c), dtype=torch.float32, device=feat.device)
-            ops.edge_rows(2, xyz.float(), new_xyz.float(), idx, out=out, out_col0=0)
-            ops.edge_rows(0, f32, None, idx, out=out, out_col0=3)
+            ops.edge_rows(ops.EDGE_ROWS_REL, xyz.float(), new_xyz.float(), idx, out=out, out_col0=0)
+            ops.edge_rows(ops.EDGE_ROWS_GROUP, f32, None, idx, out=out, out_col0=3)
         ctx.save_for_backward(idx)
         ctx.meta = (feat.shape[0], c, xyz is not None, None if xyz is None else xyz.shape[0], feat.dtype)
         # the reference concatenates fp32 coordinate offsets with feat (torch.cat promotes): half-precision features under autocast must
@@ -71,11 +71,11 @@ class _EdgeGather(torch.autograd.Function):
         col0 = 3 if with_xyz else 0
         d_feat = d_xyz = d_new = None
         if ctx.needs_input_grad[0]:
-            d_feat = ops.edge_scatter_bwd(0, ops.EdgeCSR(idx, n), g, None, ns, c, g_col0=col0).to(dtype)
+            d_feat = ops.edge_scatter_bwd(ops.EDGE_SCATTER_GROUP, ops.EdgeCSR(idx, n), g, None, ns, c, g_col0=col0).to(dtype)
         if with_xyz and ctx.needs_input_grad[1]:
-            d_xyz = ops.edge_scatter_bwd(0, ops.EdgeCSR(idx, n_xyz), g, None, ns, 3, g_col0=0)
+            d_xyz = ops.edge_scatter_bwd(ops.EDGE_SCATTER_GROUP, ops.EdgeCSR(idx, n_xyz), g, None, ns, 3, g_col0=0)
         if with_xyz and ctx.needs_input_grad[2]:
-            d_new = -ops.edge_reduce(2, None, g, None, idx, m, ns, 3, pos_stride=g.shape[-1], pos_col0=0)
+            d_new = -ops.edge_reduce(ops.EDGE_REDUCE_POS, None, g, None, idx, m, ns, 3, pos_stride=g.shape[-1], pos_col0=0)
         return d_feat, d_xyz, d_new, None
 
 
@@ -99,13 +99,13 @@ class _EdgeInterpolate(torch.autograd.Function):
         weight = weight.float().contiguous()
         ctx.save_for_backward(idx, weight)
         ctx.meta = (feat.shape[0], feat.shape[1])
-        return ops.edge_reduce(0, feat.float().contiguous(), None, weight, idx, idx.shape[0], idx.shape[1], feat.shape[1])
+        return ops.edge_reduce(ops.EDGE_REDUCE_INTERP, feat.float().contiguous(), None, weight, idx, idx.shape[0], idx.shape[1], feat.shape[1])
 
     @staticmethod
     def backward(ctx, g):
         idx, weight = ctx.saved_tensors
         n, c = ctx.meta
-        return ops.edge_scatter_bwd(2, ops.EdgeCSR(idx, n), g.float().contiguous(), weight, idx.shape[1], c), None, None
+        return ops.edge_scatter_bwd(ops.EDGE_SCATTER_INTERP, ops.EdgeCSR(idx, n), g.float().contiguous(), weight, idx.shape[1], c), None, None
 
 
 def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
@@ -206,7 +206,7 @@ class _EdgeSubtract(torch.autograd.Function):
         idx = idx.to(torch.int32).contiguous()
         ctx.save_for_backward(idx)
         ctx.meta = (input2.shape[0], input1.shape[1])
-        return ops.edge_rows(1, input2.float().contiguous(), input1.float().contiguous(), idx)
+        return ops.edge_rows(ops.EDGE_ROWS_SUB, input2.float().contiguous(), input1.float().contiguous(), idx)
 
     @staticmethod
     def backward(ctx, g):
@@ -214,8 +214,8 @@ class _EdgeSubtract(torch.autograd.Function):
         n2, c = ctx.meta
         m, ns = idx.shape
         g = g.float().contiguous()
-        d1 = ops.edge_reduce(2, None, g, None, None, m, ns, c, pos_stride=c, pos_col0=0) if ctx.needs_input_grad[0] else None
-        d2 = ops.edge_scatter_bwd(1, ops.EdgeCSR(idx, n2), g, None, ns, c) if ctx.needs_input_grad[1] else None
+        d1 = ops.edge_reduce(ops.EDGE_REDUCE_POS, None, g, None, None, m, ns, c, pos_stride=c, pos_col0=0) if ctx.needs_input_grad[0] else None
+        d2 = ops.edge_scatter_bwd(ops.EDGE_SCATTER_SUB, ops.EdgeCSR(idx, n2), g, None, ns, c) if ctx.needs_input_grad[1] else None
         return d1, d2, None
 
 
@@ -233,14 +233,14 @@ class _EdgeAggregate(torch.autograd.Function):
         input, position, weight = input.float().contiguous(), position.float().contiguous(), weight.float().contiguous()
         n, ns, c = position.shape
         ctx.save_for_backward(input, position, weight, idx)
-        return ops.edge_reduce(1, input, position, weight, idx, n, ns, c, w_c=weight.shape[-1])
+        return ops.edge_reduce(ops.EDGE_REDUCE_AGG, input, position, weight, idx, n, ns, c, w_c=weight.shape[-1])
 
     @staticmethod
     def backward(ctx, g):
         input, position, weight, idx = ctx.saved_tensors
         n, ns, c = position.shape
         g = g.float().contiguous()
-        d_in = ops.edge_scatter_bwd(3, ops.EdgeCSR(idx, input.shape[0]), g, weight, ns, c, w_c=weight.shape[-1]) if ctx.needs_input_grad[0] else None
+        d_in = ops.edge_scatter_bwd(ops.EDGE_SCATTER_AGG, ops.EdgeCSR(idx, input.shape[0]), g, weight, ns, c, w_c=weight.shape[-1]) if ctx.needs_input_grad[0] else None
         d_pos, d_w = ops.aggregation_edge_bwd(input, position, weight, idx, g)
         return d_in, d_pos, d_w, None
 

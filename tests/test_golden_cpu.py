@@ -333,7 +333,7 @@ def test_derived_signatures_match_a_pinned_sample():
     table = _lib.HEADER.signatures
     for name, want in pinned.items():
         assert tuple(table[name][:2]) == want, name
-    assert len(table) == 175 == len(re.findall(r"\bptc_\w+\s*\(", _header_without_comments()))
+    assert len(table) == 178 == len(re.findall(r"\bptc_\w+\s*\(", _header_without_comments()))
     assert _lib.exported_symbols() == sorted(table) and _lib._SIGNATURES == {name: tuple(v[:2]) for name, v in table.items()}
 
 
@@ -357,7 +357,7 @@ def test_status_calls_are_told_from_value_calls_by_the_header_rule():
                 n_value += 1
                 assert not any("*" in p for p in params), name                         # scalars only: a predicate / a query
                 assert "supported" in name or name in ("ptc_ptv3_block_abi", "ptc_ptv3_block_mlp_fused"), name
-    assert (n_status, n_value) == (119, 14)
+    assert (n_status, n_value) == (119, 16)
 
 
 @pytest.mark.parametrize("decl, named", [
