@@ -776,13 +776,21 @@ int ptc_pair_aggregate_bwd(const float* grad_out, const float* attn, const float
  *                                   parameters, tables, DropPath row scales (NULL = none); for the backward also the incoming
  *                                   gradients (either may be NULL) and the transposed weight layouts ([c_in][taps'][c_out],
  *                                   ptc_weight_layouts: conv mirrored, qkv repeated twice)
- *      out [PTC_BLK_O_COUNT]        forward outputs = what the backward reads back (`sv`): caller-allocated
- *      g   [PTC_BLK_GS_COUNT]       backward outputs: gradients (G_*; fp32 parameters' gradients, G_X0 in the dtype of x0, G_XC
- *                                   16-bit) and scratch (S_*), caller-allocated; workspace >= ptc_ptv3_block_workspace_bytes
+ *    Everything a Block produces lives in five caller-allocated slabs of different lifetimes (PTC_BLK_SLAB_*: what the forward
+ *    saves for the backward, 16-bit and fp32; the parameter gradients; the backward's fp32 and 16-bit scratch gradients).  The
+ *    library alone decides what lives where: ptc_ptv3_block_layout (host only, no GPU call) returns the slabs' byte totals and, per
+ *    slot, its slab (-1: the slot does not exist for this shape), byte offset and byte size.  Slot ids: the PTC_BLK_O_* index, or
+ *    PTC_BLK_O_COUNT + the PTC_BLK_G_* / S_* index; the arrays hold PTC_BLK_SLOT_COUNT entries, the return value (0: refused,
+ *    ptc_last_error() says why).  A caller needs the totals, and the offsets of what it hands on: G_X0, G_XC, the 18 parameter
+ *    gradients (fp32; G_X0 in the dtype of x0, G_XC 16-bit).  O_X3 / O_XB3 are in no slab: the returned tensors, separate pointers.
+ *      slabs      [PTC_BLK_SLAB_COUNT]  base pointers, 16-byte aligned (PTC_EINVAL); the forward reads the two SAVED entries only
+ *      slab_bytes [PTC_BLK_SLAB_COUNT]  their sizes: one below the layout's total is PTC_EWORKSPACE, before any launch
+ *    The backward gets the saved slabs as the forward left them, x3, and a workspace >= ptc_ptv3_block_workspace_bytes.
  *    The forward takes a workspace too (ABI 3): >= ptc_ptv3_block_fwd_workspace_bytes(n, c), the convolution's
  *    (ptc_spconv_fwd_blk_workspace_bytes; 0 for 32 / 64 channels, then NULL will do).  Nothing in it outlives the call.
+ *    ABI 4: slabs and the layout query instead of caller-filled out / sv / g pointer tables.
  * ------------------------------------------------------------------------------------------ */
-#define PTC_BLK_ABI 3
+#define PTC_BLK_ABI 4
 enum { PTC_BLK_I_ABI, PTC_BLK_I_N, PTC_BLK_I_NPAD, PTC_BLK_I_NSEQ, PTC_BLK_I_C, PTC_BLK_I_HEADS, PTC_BLK_I_DTYPE, PTC_BLK_I_A_DTYPE,
        PTC_BLK_I_PATCH, PTC_BLK_I_BLK_BM, PTC_BLK_I_BLK_HCAP, PTC_BLK_I_COUNT };
 enum { PTC_BLK_F_SCALE, PTC_BLK_F_EPS_CPE, PTC_BLK_F_EPS_N1, PTC_BLK_F_EPS_N2, PTC_BLK_F_COUNT };
@@ -801,16 +809,19 @@ enum { PTC_BLK_G_X0, PTC_BLK_G_XC, PTC_BLK_G_W_CONV, PTC_BLK_G_B_CONV, PTC_BLK_G
        PTC_BLK_G_G_N2, PTC_BLK_G_BE_N2, PTC_BLK_G_W_FC1, PTC_BLK_G_B_FC1, PTC_BLK_G_W_FC2, PTC_BLK_G_B_FC2,
        PTC_BLK_S_DX2, PTC_BLK_S_DM, PTC_BLK_S_DH, PTC_BLK_S_DY2, PTC_BLK_S_DX1, PTC_BLK_S_DA, PTC_BLK_S_DATT, PTC_BLK_S_DQKV,
        PTC_BLK_S_DY1, PTC_BLK_S_DLIN, PTC_BLK_S_DCONV, PTC_BLK_GS_COUNT };
+enum { PTC_BLK_SLAB_SAVED16, PTC_BLK_SLAB_SAVED32, PTC_BLK_SLAB_PGRAD, PTC_BLK_SLAB_SCRATCH32, PTC_BLK_SLAB_SCRATCH16, PTC_BLK_SLAB_COUNT };
+#define PTC_BLK_SLOT_COUNT 49 /* PTC_BLK_O_COUNT + PTC_BLK_GS_COUNT */
 int ptc_ptv3_block_abi(void);
-/* 1: the executor runs the Block's MLP on ptc_mlp_fwd / ptc_mlp_bwd for this (c, dtype) -- then O_H, O_ACT, O_M and S_DH are never
- * touched and need not be allocated (round 6; PTC_BLK_MLP_FUSED=0 in the environment keeps the split kernels) */
+/* 1: the executor runs the Block's MLP on ptc_mlp_fwd / ptc_mlp_bwd for this (c, dtype) -- then O_H, O_ACT, O_M and S_DH do not
+ * exist in the layout (round 6; PTC_BLK_MLP_FUSED=0 in the environment keeps the split kernels) */
 int ptc_ptv3_block_mlp_fused(int c, int dtype);
 size_t ptc_ptv3_block_workspace_bytes(int64_t n, int64_t n_pad, int c, int heads);
 size_t ptc_ptv3_block_fwd_workspace_bytes(int64_t n, int c);
-int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in, void* const* out, void* workspace,
-                       size_t workspace_bytes, ptc_stream_t stream);
-int ptc_ptv3_block_bwd(const int64_t* iv, const float* fv, const void* const* in, const void* const* sv, void* const* g,
-                       void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+size_t ptc_ptv3_block_layout(const int64_t* iv, int64_t* slab_bytes, int64_t* slot_slab, int64_t* slot_offset, int64_t* slot_bytes);
+int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in, void* const* slabs, const int64_t* slab_bytes,
+                       void* x3, void* xb3, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
+int ptc_ptv3_block_bwd(const int64_t* iv, const float* fv, const void* const* in, void* const* slabs, const int64_t* slab_bytes,
+                       const void* x3, void* workspace, size_t workspace_bytes, ptc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Q. OA-CNNs adaptive aggregation (pointcept/models/oacnns/oacnns_v1m1_base.py:87-111,160-164), csrc/cluster_agg.hip.

@@ -124,7 +124,7 @@ def exported_symbols():
 
 
 def block_enums():
-    """name -> index of the PTC_BLK_* argument tables of ptc_ptv3_block_fwd / _bwd, and "ABI" -> PTC_BLK_ABI, as include/ptcore.h
+    """name -> index of the PTC_BLK_* argument tables, slabs and slots of ptc_ptv3_block_fwd / _bwd / _layout, and "ABI" -> PTC_BLK_ABI, as include/ptcore.h
     defines them (the header the library was compiled against -- lib() checks its hash)."""
     return _BLK_ENUMS
 

@@ -5,8 +5,9 @@
 // interpreter + ctypes + allocator work per Function (profiles/r02_y_ddp_single_rank.txt: a 2 x 20000-voxel step cost 37 ms, the
 // 8 x 102400-voxel one 32 ms of host time): the floor under any kernel work, and what 8 ranks sharing one host contend for.  The 22
 // Blocks are 2/3 of those launches.  Here a Block is ONE autograd Function (functional._BlockFn) whose forward / backward make ONE
-// call into this file with a table of pointers (activations saved for the backward live in slabs the caller allocated with two
-// torch.empty calls); the arithmetic is the SAME sequence of the library's own entry points the Python-composed path issues
+// call into this file with a table of input pointers and the base pointers of five slabs; what lives where inside the slabs is
+// decided here alone (BLK_SLOTS below: the caller asks ptc_ptv3_block_layout for the totals and allocates, nothing else); the
+// arithmetic is the SAME sequence of the library's own entry points the Python-composed path issues
 // (ptc_spconv_fwd[_blk], ptc_linear_fwd_ex, ptc_add_norm_*, ptc_attn_varlen_*, ptc_spconv_wgrad, ptc_column_sum) with the same
 // operands: bit-identical results (tests/test_host_emulation_cpu.py, tests/test_gpu_model.py).
 //
@@ -16,6 +17,8 @@
 #define PTC_BLK_JOINT_EPILOGUE 1     // 0: timing A/B only (`python -m pointcept_amd.build --variant d_PTC_BLK_JOINT_EPILOGUE_0`)
 #endif
 #include "spconv_internal.h"
+#include <cstdint>
+#include <cstring>
 
 #define RUN(call)               \
   do {                          \
@@ -29,8 +32,8 @@ template <typename T> static inline T* M(void* const* p, int i) { return (T*)p[i
 extern "C" int ptc_ptv3_block_abi(void) { return PTC_BLK_ABI; }
 
 // Round 6: the MLP of a Block (steps 8 + 9 / 9' + 8') on csrc/mlp.hip's one kernel per direction where it exists (C = 32 | 64: the
-// 819200- and ~200000-row stages).  Then H / ACT / M of the forward's slab and DH of the backward's are never touched (the caller need not
-// allocate them: functional._blk_plan asks this function), the backward recomputes h.  PTC_BLK_MLP_FUSED=0: the split kernels (A/B).
+// 819200- and ~200000-row stages).  Then H / ACT / M of the forward's slab and DH of the backward's do not exist (BLK_SLOTS: SPLIT_MLP),
+// the backward recomputes h.  PTC_BLK_MLP_FUSED=0: the split kernels (A/B).
 extern "C" int ptc_ptv3_block_mlp_fused(int c, int dtype) {
   static const int off = [] { const char* e = getenv("PTC_BLK_MLP_FUSED"); return e && e[0] == '0'; }();
   return !off && ptc_mlp_supported(c, dtype);
@@ -64,26 +67,140 @@ static BlkWs blk_ws(int64_t n, int64_t n_pad, int c, int heads) {
 
 extern "C" size_t ptc_ptv3_block_workspace_bytes(int64_t n, int64_t n_pad, int c, int heads) { return blk_ws(n, n_pad, c, heads).total; }
 
+// ---- memory plan ----------------------------------------------------------------------------------------------------------------
+// Everything a Block produces lives in five slabs of different lifetimes (PTC_BLK_SLAB_*): what the forward saves for the backward
+// (16-bit, fp32), the parameter gradients (small and long-lived: AccumulateGrad and DDP buckets keep views of it), and the
+// backward's transient fp32 and 16-bit gradients.  BLK_SLOTS is the ONE statement of which slot lives in which slab, of which shape
+// and under which condition; a slab is its rows' pieces in table order, each rounded up to 256 bytes.  The element size is the
+// slab's.  (X3 / XB3 are the returned tensors: the caller's own allocations, in no slab.)
+enum BlkDim : uint8_t { D_1, D_2, D_N, D_NPAD, D_C, D_3C, D_4C, D_27C, D_HEADS };
+enum BlkWhen : uint8_t { ALWAYS, SPLIT_MLP, X0_F32, X0_16BIT };      // SPLIT_MLP: not ptc_ptv3_block_mlp_fused; X0_*: the stream's dtype
+struct BlkSlab { const char* name; int elem; };
+static const BlkSlab BLK_SLABS[PTC_BLK_SLAB_COUNT] = {{"saved16", 2}, {"saved32", 4}, {"param_grad", 4}, {"scratch32", 4}, {"scratch16", 2}};
+struct BlkSlot { uint8_t slot, slab; BlkDim rows, cols; BlkWhen when; };
+#define SV(name) PTC_BLK_O_##name
+#define GS(name) (PTC_BLK_O_COUNT + PTC_BLK_##name)       // slot ids: the O_* indices, then the G_* / S_* ones
+static const BlkSlot BLK_SLOTS[] = {
+    {SV(CONV), PTC_BLK_SLAB_SAVED16, D_N, D_C, ALWAYS},       {SV(LIN), PTC_BLK_SLAB_SAVED16, D_N, D_C, ALWAYS},
+    {SV(Y1), PTC_BLK_SLAB_SAVED16, D_N, D_C, ALWAYS},         {SV(QKV), PTC_BLK_SLAB_SAVED16, D_NPAD, D_3C, ALWAYS},
+    {SV(ATT), PTC_BLK_SLAB_SAVED16, D_NPAD, D_C, ALWAYS},     {SV(A), PTC_BLK_SLAB_SAVED16, D_N, D_C, ALWAYS},
+    {SV(Y2), PTC_BLK_SLAB_SAVED16, D_N, D_C, ALWAYS},         {SV(H), PTC_BLK_SLAB_SAVED16, D_N, D_4C, SPLIT_MLP},
+    {SV(ACT), PTC_BLK_SLAB_SAVED16, D_N, D_4C, SPLIT_MLP},    {SV(M), PTC_BLK_SLAB_SAVED16, D_N, D_C, SPLIT_MLP},
+
+    {SV(X1), PTC_BLK_SLAB_SAVED32, D_N, D_C, ALWAYS},         {SV(X2), PTC_BLK_SLAB_SAVED32, D_N, D_C, ALWAYS},
+    {SV(ST_CPE), PTC_BLK_SLAB_SAVED32, D_2, D_N, ALWAYS},     {SV(ST_N1), PTC_BLK_SLAB_SAVED32, D_2, D_N, ALWAYS},
+    {SV(ST_N2), PTC_BLK_SLAB_SAVED32, D_2, D_N, ALWAYS},      {SV(LSE), PTC_BLK_SLAB_SAVED32, D_HEADS, D_NPAD, ALWAYS},
+
+    {GS(G_W_CONV), PTC_BLK_SLAB_PGRAD, D_27C, D_C, ALWAYS},   {GS(G_B_CONV), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},
+    {GS(G_W_LIN), PTC_BLK_SLAB_PGRAD, D_C, D_C, ALWAYS},      {GS(G_B_LIN), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},
+    {GS(G_G_CPE), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},      {GS(G_BE_CPE), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},
+    {GS(G_G_N1), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},       {GS(G_BE_N1), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},
+    {GS(G_W_QKV), PTC_BLK_SLAB_PGRAD, D_3C, D_C, ALWAYS},     {GS(G_B_QKV), PTC_BLK_SLAB_PGRAD, D_1, D_3C, ALWAYS},
+    {GS(G_W_PROJ), PTC_BLK_SLAB_PGRAD, D_C, D_C, ALWAYS},     {GS(G_B_PROJ), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},
+    {GS(G_G_N2), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},       {GS(G_BE_N2), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},
+    {GS(G_W_FC1), PTC_BLK_SLAB_PGRAD, D_4C, D_C, ALWAYS},     {GS(G_B_FC1), PTC_BLK_SLAB_PGRAD, D_1, D_4C, ALWAYS},
+    {GS(G_W_FC2), PTC_BLK_SLAB_PGRAD, D_C, D_4C, ALWAYS},     {GS(G_B_FC2), PTC_BLK_SLAB_PGRAD, D_1, D_C, ALWAYS},
+
+    {GS(S_DX2), PTC_BLK_SLAB_SCRATCH32, D_N, D_C, ALWAYS},    {GS(S_DX1), PTC_BLK_SLAB_SCRATCH32, D_N, D_C, ALWAYS},
+    {GS(G_X0), PTC_BLK_SLAB_SCRATCH32, D_N, D_C, X0_F32},
+
+    {GS(S_DM), PTC_BLK_SLAB_SCRATCH16, D_N, D_C, ALWAYS},     {GS(S_DH), PTC_BLK_SLAB_SCRATCH16, D_N, D_4C, SPLIT_MLP},
+    {GS(S_DY2), PTC_BLK_SLAB_SCRATCH16, D_N, D_C, ALWAYS},    {GS(S_DA), PTC_BLK_SLAB_SCRATCH16, D_N, D_C, ALWAYS},
+    {GS(S_DATT), PTC_BLK_SLAB_SCRATCH16, D_NPAD, D_C, ALWAYS}, {GS(S_DQKV), PTC_BLK_SLAB_SCRATCH16, D_NPAD, D_3C, ALWAYS},
+    {GS(S_DY1), PTC_BLK_SLAB_SCRATCH16, D_N, D_C, ALWAYS},    {GS(S_DLIN), PTC_BLK_SLAB_SCRATCH16, D_N, D_C, ALWAYS},
+    {GS(S_DCONV), PTC_BLK_SLAB_SCRATCH16, D_N, D_C, ALWAYS},  {GS(G_XC), PTC_BLK_SLAB_SCRATCH16, D_N, D_C, ALWAYS},
+    {GS(G_X0), PTC_BLK_SLAB_SCRATCH16, D_N, D_C, X0_16BIT},
+};
+#undef SV
+#undef GS
+static_assert(PTC_BLK_SLOT_COUNT == PTC_BLK_O_COUNT + PTC_BLK_GS_COUNT, "PTC_BLK_SLOT_COUNT: the O_* slots, then the G_* / S_* ones");
+// the 18 parameters stand in the same order among the inputs and among the gradients (blk_bind: no parameter, no gradient)
+#define SAME_PLACE(name) static_assert(PTC_BLK_P_##name - PTC_BLK_P_W_CONV == PTC_BLK_G_##name - PTC_BLK_G_W_CONV, "parameter order: " #name)
+SAME_PLACE(W_CONV); SAME_PLACE(B_CONV); SAME_PLACE(W_LIN);  SAME_PLACE(B_LIN);  SAME_PLACE(G_CPE); SAME_PLACE(BE_CPE);
+SAME_PLACE(G_N1);   SAME_PLACE(BE_N1);  SAME_PLACE(W_QKV);  SAME_PLACE(B_QKV);  SAME_PLACE(W_PROJ); SAME_PLACE(B_PROJ);
+SAME_PLACE(G_N2);   SAME_PLACE(BE_N2);  SAME_PLACE(W_FC1);  SAME_PLACE(B_FC1);  SAME_PLACE(W_FC2); SAME_PLACE(B_FC2);
+#undef SAME_PLACE
+static_assert(PTC_BLK_P_B_FC2 - PTC_BLK_P_W_CONV == 17, "18 parameters, consecutive");
+
+// slab < 0: the slot does not exist for this shape (or is the caller's own tensor)
+struct BlkLayout { int64_t slab_bytes[PTC_BLK_SLAB_COUNT]; int64_t slab[PTC_BLK_SLOT_COUNT], off[PTC_BLK_SLOT_COUNT], bytes[PTC_BLK_SLOT_COUNT]; };
+static BlkLayout blk_layout(int64_t n, int64_t n_pad, int c, int heads, int dt, int a_dt) {
+  const int64_t dim[] = {1, 2, n, n_pad, c, 3 * (int64_t)c, 4 * (int64_t)c, 27 * (int64_t)c, heads};
+  const bool split = !ptc_ptv3_block_mlp_fused(c, dt), x0_f32 = a_dt == PTC_F32;
+  BlkLayout L = {};
+  for (int i = 0; i < PTC_BLK_SLOT_COUNT; ++i) L.slab[i] = -1;
+  for (const BlkSlot& t : BLK_SLOTS) {
+    if ((t.when == SPLIT_MLP && !split) || (t.when == X0_F32 && !x0_f32) || (t.when == X0_16BIT && x0_f32)) continue;
+    L.slab[t.slot] = t.slab;
+    L.off[t.slot] = L.slab_bytes[t.slab];
+    L.bytes[t.slot] = dim[t.rows] * dim[t.cols] * BLK_SLABS[t.slab].elem;
+    L.slab_bytes[t.slab] += (int64_t)ptc_align_up((size_t)L.bytes[t.slot], 256);
+  }
+  return L;
+}
+
+static int blk_check_shape(const char* who, const int64_t* iv) {
+  PTC_REQUIRE(iv[PTC_BLK_I_ABI] == PTC_BLK_ABI, PTC_EINVAL, "%s: argument tables of another ABI revision", who);
+  const int64_t n = iv[PTC_BLK_I_N], np = iv[PTC_BLK_I_NPAD];
+  const int c = (int)iv[PTC_BLK_I_C], H = (int)iv[PTC_BLK_I_HEADS], dt = (int)iv[PTC_BLK_I_DTYPE], hid = 4 * c;
+  // f16 (round 4): the reference's fp16-autocast recipe -- every GEMM, joint and convolution on f16 operands; the window attention
+  // keeps its bf16 arithmetic and does the call site's casts (ptv3m1:209,215) in its load / store paths (attention.hip, F16 I/O)
+  PTC_REQUIRE(dt == PTC_BF16 || dt == PTC_F16, PTC_EUNSUPPORTED, "%s: 16-bit GEMM operands only", who);
+  // (c <= 256: linear2's range; wider Blocks -- stage 4 of PT-v3m1, 512 channels -- when the MLP GEMMs with their GELU epilogues exist at that
+  //  width: gemm3.h)
+  PTC_REQUIRE(c > 0 && c % 16 == 0 && H * 16 == c && (c <= 256 || (c <= 512 && ptc_linear_supported_ex(c, hid, dt))), PTC_EUNSUPPORTED,
+              "%s: c=%d heads=%d (head_dim 16, c <= 256, or <= 512 with the wide GEMM kernels)", who, c, H);
+  PTC_REQUIRE(n >= 0 && np >= 0, PTC_EINVAL, "%s: n=%lld n_pad=%lld", who, (long long)n, (long long)np);
+  return PTC_OK;
+}
+
+// Host only (no GPU call): the slab totals and, per slot id (O_* index, or PTC_BLK_O_COUNT + G_* / S_* index), its slab (-1: none),
+// byte offset and byte size.  Returns PTC_BLK_SLOT_COUNT, or 0 with ptc_last_error() set.
+extern "C" size_t ptc_ptv3_block_layout(const int64_t* iv, int64_t* slab_bytes, int64_t* slot_slab, int64_t* slot_offset, int64_t* slot_bytes) {
+  if (!(iv && slab_bytes && slot_slab && slot_offset && slot_bytes)) { ptc_set_error("ptc_ptv3_block_layout: null argument"); return 0; }
+  if (blk_check_shape("ptc_ptv3_block_layout", iv) != PTC_OK) return 0;
+  const BlkLayout L = blk_layout(iv[PTC_BLK_I_N], iv[PTC_BLK_I_NPAD], (int)iv[PTC_BLK_I_C], (int)iv[PTC_BLK_I_HEADS], (int)iv[PTC_BLK_I_DTYPE],
+                                 (int)iv[PTC_BLK_I_A_DTYPE]);
+  memcpy(slab_bytes, L.slab_bytes, sizeof L.slab_bytes);
+  memcpy(slot_slab, L.slab, sizeof L.slab);
+  memcpy(slot_offset, L.off, sizeof L.off);
+  memcpy(slot_bytes, L.bytes, sizeof L.bytes);
+  return PTC_BLK_SLOT_COUNT;
+}
+
+// The caller's slabs [first, last] against the layout (large enough, 16-byte aligned: before any launch), then the address of every
+// slot that lives in one of them; the others stay NULL.  A parameter that is absent (NULL among the inputs) has no gradient.
+static int blk_bind(const char* who, const BlkLayout& L, const void* const* in, void* const* slabs, const int64_t* slab_bytes, int first, int last,
+                    void** slot) {
+  for (int b = first; b <= last; ++b) {
+    PTC_REQUIRE(slab_bytes[b] >= L.slab_bytes[b], PTC_EWORKSPACE, "%s: workspace: slab %s holds %lld bytes, the layout needs %lld", who,
+                BLK_SLABS[b].name, (long long)slab_bytes[b], (long long)L.slab_bytes[b]);
+    PTC_REQUIRE(L.slab_bytes[b] == 0 || (slabs[b] && (uintptr_t)slabs[b] % 16 == 0), PTC_EINVAL, "%s: slab %s is not 16-byte aligned", who,
+                BLK_SLABS[b].name);
+  }
+  for (int i = 0; i < PTC_BLK_SLOT_COUNT; ++i)
+    slot[i] = L.slab[i] >= first && L.slab[i] <= last ? (char*)slabs[L.slab[i]] + L.off[i] : nullptr;
+  for (int k = 0; k < 18; ++k)
+    if (!in[PTC_BLK_P_W_CONV + k]) slot[PTC_BLK_O_COUNT + PTC_BLK_G_W_CONV + k] = nullptr;
+  return PTC_OK;
+}
+
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 // workspace of the forward: the convolution's alone (0 for the 32- / 64-channel Blocks; nothing in it outlives the call)
 extern "C" size_t ptc_ptv3_block_fwd_workspace_bytes(int64_t n, int c) { return ptc_spconv_fwd_blk_workspace_bytes(n, 27, c, c); }
 
-extern "C" int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in, void* const* out, void* workspace,
-                                  size_t workspace_bytes, ptc_stream_t s) {
-  PTC_REQUIRE(iv && fv && in && out, PTC_EINVAL, "ptc_ptv3_block_fwd: null argument table");
-  PTC_REQUIRE(iv[PTC_BLK_I_ABI] == PTC_BLK_ABI, PTC_EINVAL, "ptc_ptv3_block_fwd: argument tables of another ABI revision");
+extern "C" int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void* const* in, void* const* slabs, const int64_t* slab_bytes,
+                                  void* x3, void* xb3, void* workspace, size_t workspace_bytes, ptc_stream_t s) {
+  PTC_REQUIRE(iv && fv && in && slabs && slab_bytes, PTC_EINVAL, "ptc_ptv3_block_fwd: null argument table");
+  RUN(blk_check_shape("ptc_ptv3_block_fwd", iv));
   const int64_t n = iv[PTC_BLK_I_N], np = iv[PTC_BLK_I_NPAD], n_seq = iv[PTC_BLK_I_NSEQ];
   const int c = (int)iv[PTC_BLK_I_C], H = (int)iv[PTC_BLK_I_HEADS], dt = (int)iv[PTC_BLK_I_DTYPE], hid = 4 * c;
   const int a_dt = (int)iv[PTC_BLK_I_A_DTYPE], patch = (int)iv[PTC_BLK_I_PATCH];
   const size_t ws_need = ptc_ptv3_block_fwd_workspace_bytes(n, c);
   PTC_REQUIRE(ws_need == 0 || (workspace && workspace_bytes >= ws_need), PTC_EWORKSPACE, "ptc_ptv3_block_fwd: workspace too small");
-  // f16 (round 4): the reference's fp16-autocast recipe -- every GEMM, joint and convolution on f16 operands; the window attention
-  // keeps its bf16 arithmetic and does the call site's casts (ptv3m1:209,215) in its load / store paths (attention.hip, F16 I/O)
-  PTC_REQUIRE(dt == PTC_BF16 || dt == PTC_F16, PTC_EUNSUPPORTED, "ptc_ptv3_block_fwd: 16-bit GEMM operands only");
-  // (c <= 256: linear2's range; wider Blocks -- stage 4 of PT-v3m1, 512 channels -- when the MLP GEMMs with their GELU epilogues exist at that
-  //  width: gemm3.h)
-  PTC_REQUIRE(c % 16 == 0 && H * 16 == c && (c <= 256 || (c <= 512 && ptc_linear_supported_ex(c, hid, dt))), PTC_EUNSUPPORTED,
-              "ptc_ptv3_block_fwd: c=%d heads=%d (head_dim 16, c <= 256, or <= 512 with the wide GEMM kernels)", c, H);
+  void* out[PTC_BLK_SLOT_COUNT];
+  RUN(blk_bind("ptc_ptv3_block_fwd", blk_layout(n, np, c, H, dt, a_dt), in, slabs, slab_bytes, PTC_BLK_SLAB_SAVED16, PTC_BLK_SLAB_SAVED32, out));
+  out[PTC_BLK_O_X3] = x3, out[PTC_BLK_O_XB3] = xb3;
   if (n == 0) return PTC_OK;
   const int32_t* nbr = (const int32_t*)P(in, PTC_BLK_P_NBR);
   // 1. positional encoding: 3^3 submanifold convolution (ptv3m1:278-284) ...
@@ -150,16 +267,21 @@ extern "C" int ptc_ptv3_block_fwd(const int64_t* iv, const float* fv, const void
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------------------
-// `in`: the forward's inputs and saved outputs under the same indices plus the incoming gradients and the transposed weight
-// layouts; `out`: gradients (PTC_BLK_G_*) and scratch activations gradients (PTC_BLK_S_*), all caller-allocated.
-extern "C" int ptc_ptv3_block_bwd(const int64_t* iv, const float* fv, const void* const* in, const void* const* sv, void* const* g,
-                                  void* workspace, size_t workspace_bytes, ptc_stream_t s) {
-  PTC_REQUIRE(iv && fv && in && sv && g && workspace, PTC_EINVAL, "ptc_ptv3_block_bwd: null argument table");
-  PTC_REQUIRE(iv[PTC_BLK_I_ABI] == PTC_BLK_ABI, PTC_EINVAL, "ptc_ptv3_block_bwd: argument tables of another ABI revision");
+// `in`: the forward's inputs under the same indices plus the incoming gradients and the transposed weight layouts; the saved slabs
+// as the forward left them and x3; gradients (PTC_BLK_G_*) and scratch activation gradients (PTC_BLK_S_*) go to the other three slabs.
+extern "C" int ptc_ptv3_block_bwd(const int64_t* iv, const float* fv, const void* const* in, void* const* slabs, const int64_t* slab_bytes,
+                                  const void* x3, void* workspace, size_t workspace_bytes, ptc_stream_t s) {
+  PTC_REQUIRE(iv && fv && in && slabs && slab_bytes && workspace, PTC_EINVAL, "ptc_ptv3_block_bwd: null argument table");
+  RUN(blk_check_shape("ptc_ptv3_block_bwd", iv));
   const int64_t n = iv[PTC_BLK_I_N], np = iv[PTC_BLK_I_NPAD], n_seq = iv[PTC_BLK_I_NSEQ];
   const int c = (int)iv[PTC_BLK_I_C], H = (int)iv[PTC_BLK_I_HEADS], dt = (int)iv[PTC_BLK_I_DTYPE], hid = 4 * c;
   const int a_dt = (int)iv[PTC_BLK_I_A_DTYPE], patch = (int)iv[PTC_BLK_I_PATCH];
   PTC_REQUIRE(workspace_bytes >= ptc_ptv3_block_workspace_bytes(n, np, c, H), PTC_EWORKSPACE, "ptc_ptv3_block_bwd: workspace too small");
+  void* slot[PTC_BLK_SLOT_COUNT];
+  RUN(blk_bind("ptc_ptv3_block_bwd", blk_layout(n, np, c, H, dt, a_dt), in, slabs, slab_bytes, PTC_BLK_SLAB_SAVED16, PTC_BLK_SLAB_SCRATCH16, slot));
+  slot[PTC_BLK_O_X3] = (void*)x3;
+  const void* const* sv = slot;
+  void* const* g = slot + PTC_BLK_O_COUNT;
   if (n == 0) return PTC_OK;
   const int32_t* nbr = (const int32_t*)P(in, PTC_BLK_P_NBR);
   const float* rs1 = (const float*)P(in, PTC_BLK_P_RS1);

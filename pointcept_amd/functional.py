@@ -1084,59 +1084,46 @@ _BLK_PARAMS = ("W_CONV", "B_CONV", "W_LIN", "B_LIN", "G_CPE", "BE_CPE", "G_N1", 
 _BLK_WEIGHTS = ("W_CONV", "W_LIN", "W_QKV", "W_PROJ", "W_FC1", "W_FC2")
 
 
-def _blk_layout(items, elem_bytes):
-    """[(name, rows, cols)] -> ({name: (byte offset, rows, cols)}, total elements): consecutive 256-byte aligned pieces of one allocation"""
-    unit, off, out = 256 // elem_bytes, 0, {}
-    for name, rows, cols in items:
-        out[name] = (off * elem_bytes, int(rows), int(cols))
-        off += (int(rows) * int(cols) + unit - 1) // unit * unit
-    return out, max(off, 1)
+def _blk_alloc(nbytes, dtype, device):
+    """one slab of a Block call: `nbytes` bytes (a multiple of 256) of `dtype`.  Every slab of _BlockFn is allocated here and nowhere else."""
+    return torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=device)
 
 
 _blk_plans = {}
 
 
-def _blk_plan(n, npad, c, heads, x0_f32, dt=torch.bfloat16):
-    """pointer-table layout of one Block call, cached per shape: byte offsets of every saved activation / scratch gradient inside
-    the slabs, as (table index, offset) lists -- the per-call work is then two allocations and ~45 integer stores per direction"""
-    # round 6: where the executor runs the MLP on csrc/mlp.hip (C = 32 | 64) the hidden-width tensors do not exist: no H / ACT / M in the
-    # saved slab (2 x N x 4C x 2 bytes per Block: 0.84 GB at N = 819200, C = 64), no DH in the backward's scratch
-    fused = ops.block_mlp_fused(c, dt)
-    key = (n, npad, c, heads, x0_f32, fused)
+def _blk_plan(E, iv, key):
+    """the memory plan of one Block call as csrc/block_exec.hip lays it out (ptc_ptv3_block_layout: host code, no launch), cached
+    per key = (n, n_pad, c, heads, dtype of x0, dt): the byte totals of the five slabs and, for the slots this side hands on (dx0,
+    dxc, the parameter gradients), where they lie -- name -> (slab, first byte, one past the last)"""
     p = _blk_plans.get(key)
     if p is not None:
         return p
-    E = _lib.block_enums()
-    hid = 4 * c
-    l16, t16 = _blk_layout([("CONV", n, c), ("LIN", n, c), ("Y1", n, c), ("QKV", npad, 3 * c), ("ATT", npad, c), ("A", n, c), ("Y2", n, c)] +
-                           ([] if fused else [("H", n, hid), ("ACT", n, hid), ("M", n, c)]), 2)
-    l32, t32 = _blk_layout([("X1", n, c), ("X2", n, c), ("ST_CPE", 2, n), ("ST_N1", 2, n), ("ST_N2", 2, n), ("LSE", heads, npad)], 4)
-    shapes = {"W_CONV": (c, 27, c), "B_CONV": (c,), "W_LIN": (c, c), "B_LIN": (c,), "G_CPE": (c,), "BE_CPE": (c,), "G_N1": (c,), "BE_N1": (c,),
-              "W_QKV": (3 * c, c), "B_QKV": (3 * c,), "W_PROJ": (c, c), "B_PROJ": (c,), "G_N2": (c,), "BE_N2": (c,), "W_FC1": (hid, c), "B_FC1": (hid,),
-              "W_FC2": (c, hid), "B_FC2": (c,)}
-    # the parameter gradients in their OWN small slab (~12 C^2 floats): AccumulateGrad keeps the returned views -- and with them their
-    # storage -- alive as long as .grad lives; sharing a slab with the 3 N C floats of fp32 scratch pinned ~77 MB per stage-0 Block
-    # (ADVICE r3).  The fp32 scratch gradients (and dx0 of an fp32 stream) live in a second, transient slab.
-    lg, tg = _blk_layout([("G_" + k, 1, int(torch.Size(shapes[k]).numel())) for k in _BLK_PARAMS], 4)
-    gs_items = [("S_DX2", n, c), ("S_DX1", n, c)]
-    if x0_f32:
-        gs_items.append(("G_X0", n, c))
-    lgs, tgs = _blk_layout(gs_items, 4)
-    s_items = [("S_DM", n, c)] + ([] if fused else [("S_DH", n, hid)]) + [("S_DY2", n, c), ("S_DA", n, c), ("S_DATT", npad, c), ("S_DQKV", npad, 3 * c), ("S_DY1", n, c),
-               ("S_DLIN", n, c), ("S_DCONV", n, c), ("G_XC", n, c)]
-    if not x0_f32:
-        s_items.append(("G_X0", n, c))
-    ls, ts = _blk_layout(s_items, 2)
-    p = dict(E=E, t16=t16, t32=t32, tg=tg, tgs=tgs, ts=ts,
-             o16=[(E["O_" + k], v[0]) for k, v in l16.items()], o32=[(E["O_" + k], v[0]) for k, v in l32.items()],
-             g32=[(E[k], v[0]) for k, v in lg.items()], g32s=[(E[k], v[0]) for k, v in lgs.items()], g16=[(E[k], v[0]) for k, v in ls.items()],
-             gparam={k: (lg["G_" + k][0] // 4, int(torch.Size(shapes[k]).numel())) for k in _BLK_PARAMS},
-             gx0=(lgs["G_X0"][0] // 4 if x0_f32 else ls["G_X0"][0] // 2), gxc=ls["G_XC"][0] // 2,
-             ws=None, ws_fwd=None)
+    import ctypes
+
+    totals = (ctypes.c_int64 * E["SLAB_COUNT"])()
+    slab, off, size = ((ctypes.c_int64 * E["SLOT_COUNT"])() for _ in range(3))
+    if ops.lib().ptc_ptv3_block_layout(iv, totals, slab, off, size) != E["SLOT_COUNT"]:
+        raise PtcoreError("ptc_ptv3_block_layout: " + ops.lib().ptc_last_error().decode("utf-8", "replace"))
+    cut = {}
+    for name in ("G_X0", "G_XC") + tuple("G_" + k for k in _BLK_PARAMS):
+        i = E["O_COUNT"] + E[name]
+        cut[name] = (slab[i], off[i], off[i] + size[i])
+    p = dict(bytes=tuple(totals), cut=cut, ws=None, ws_fwd=None)
     if len(_blk_plans) > 256:
         _blk_plans.clear()
     _blk_plans[key] = p
     return p
+
+
+def _blk_slab_args(E, slabs):
+    """{slab index: tensor} -> the arrays of base pointers and byte sizes the executor's entry points take"""
+    import ctypes
+
+    ptrs, sizes = (ctypes.c_void_p * E["SLAB_COUNT"])(), (ctypes.c_int64 * E["SLAB_COUNT"])()
+    for i, t in slabs.items():
+        ptrs[i], sizes[i] = t.data_ptr(), t.numel() * t.element_size()
+    return ptrs, sizes
 
 
 def _blk_tables(E, x0, meta):
@@ -1176,9 +1163,9 @@ class _BlockFn(Function):
         dev = x0.device
         x0 = x0.contiguous()
         xc = xc.contiguous()
-        plan = _blk_plan(n, npad, c, heads, x0.dtype == torch.float32, dt)
-        E = plan["E"]
+        E = _lib.block_enums()
         iv, fv, pin = _blk_tables(E, x0, meta)
+        plan = _blk_plan(E, iv, (n, npad, c, heads, x0.dtype, dt))
         keep = []                                            # tensors the pointer table names (alive until saved / returned)
         for k, p in zip(_BLK_PARAMS, params):
             if p is None:
@@ -1196,26 +1183,20 @@ class _BlockFn(Function):
             pin[E["P_RS1"]] = rs1.data_ptr()
         if rs2 is not None:
             pin[E["P_RS2"]] = rs2.data_ptr()
-        buf16 = torch.empty(plan["t16"], dtype=dt, device=dev)
-        buf32 = torch.empty(plan["t32"], dtype=torch.float32, device=dev)
+        # what the backward reads back: two slabs, laid out by the library (16-bit activations; fp32 streams, LayerNorm statistics, lse)
+        buf16 = _blk_alloc(plan["bytes"][E["SLAB_SAVED16"]], dt, dev)
+        buf32 = _blk_alloc(plan["bytes"][E["SLAB_SAVED32"]], torch.float32, dev)
+        pslab, nslab = _blk_slab_args(E, {E["SLAB_SAVED16"]: buf16, E["SLAB_SAVED32"]: buf32})
         x3 = torch.empty((n, c), dtype=torch.float32, device=dev)
         xb3 = torch.empty((n, c), dtype=dt, device=dev)
-        import ctypes
-
-        pout = (ctypes.c_void_p * E["O_COUNT"])()
-        b16, b32 = buf16.data_ptr(), buf32.data_ptr()
-        for idx, off in plan["o16"]:
-            pout[idx] = b16 + off
-        for idx, off in plan["o32"]:
-            pout[idx] = b32 + off
-        pout[E["O_X3"]], pout[E["O_XB3"]] = x3.data_ptr(), xb3.data_ptr()
         if plan["ws_fwd"] is None:
             plan["ws_fwd"] = int(ops.lib().ptc_ptv3_block_fwd_workspace_bytes(n, c))
         nbytes = plan["ws_fwd"]
         # transient (the convolution's fragment-ordered weights at 128 channels and more): NOT saved for the backward
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-        ops.lib().ptc_ptv3_block_fwd(iv, fv, pin, pout, None if ws is None else ws.data_ptr(), nbytes, ops.stream_ptr())
-        ctx.save_for_backward(x0, xc, rs1, rs2, buf16, buf32, x3, xb3, *keep)
+        ops.lib().ptc_ptv3_block_fwd(iv, fv, pin, pslab, nslab, x3.data_ptr(), xb3.data_ptr(), None if ws is None else ws.data_ptr(), nbytes,
+                                     ops.stream_ptr())
+        ctx.save_for_backward(x0, xc, rs1, rs2, buf16, buf32, x3, *keep)
         ctx.meta, ctx.plan = meta, plan
         ctx.present = [p is not None for p in params]
         ctx.param_dtypes = [None if p is None else p.dtype for p in params]
@@ -1226,21 +1207,19 @@ class _BlockFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz3, dyb3):
-        import ctypes
-
         n_par = len(_BLK_PARAMS)
         if dz3 is None and dyb3 is None:
             return (None,) * (5 + n_par)
         sv = ctx.saved_tensors
-        x0, xc, rs1, rs2, buf16, buf32, x3, xb3 = sv[:8]
+        x0, xc, rs1, rs2, buf16, buf32, x3 = sv[:7]
         meta, plan = ctx.meta, ctx.plan
-        E = plan["E"]
+        E = _lib.block_enums()
         dt = meta["dt"]
         n, c = x0.shape
         npad, heads = meta["n_pad"], meta["heads"]
         dev = x0.device
         iv, fv, pin = _blk_tables(E, x0, meta)
-        it = iter(sv[8:])
+        it = iter(sv[7:])
         sh = {}
         keep_wt = []
         for k, present in zip(_BLK_PARAMS, ctx.present):
@@ -1272,41 +1251,31 @@ class _BlockFn(Function):
             pin[E["P_DZ3"]] = dz3c.data_ptr()
         if dyb3c is not None:
             pin[E["P_DYB3"]] = dyb3c.data_ptr()
-        psv = (ctypes.c_void_p * E["O_COUNT"])()
-        b16, b32 = buf16.data_ptr(), buf32.data_ptr()
-        for idx, off in plan["o16"]:
-            psv[idx] = b16 + off
-        for idx, off in plan["o32"]:
-            psv[idx] = b32 + off
-        psv[E["O_X3"]], psv[E["O_XB3"]] = x3.data_ptr(), xb3.data_ptr()
-        gbuf = torch.empty(plan["tg"], dtype=torch.float32, device=dev)          # parameter gradients only (small, long-lived)
-        gscr = torch.empty(plan["tgs"], dtype=torch.float32, device=dev)         # fp32 scratch gradients (+ dx0 of an fp32 stream)
-        sbuf = torch.empty(plan["ts"], dtype=dt, device=dev)
-        pg = (ctypes.c_void_p * E["GS_COUNT"])()
-        bg, bgs, bs = gbuf.data_ptr(), gscr.data_ptr(), sbuf.data_ptr()
-        for idx, off in plan["g32"]:
-            pg[idx] = bg + off
-        for idx, off in plan["g32s"]:
-            pg[idx] = bgs + off
-        for idx, off in plan["g16"]:
-            pg[idx] = bs + off
-        for k, present in zip(_BLK_PARAMS, ctx.present):
-            if not present:
-                pg[E["G_" + k]] = None
+        # parameter gradients in their OWN small slab (~12 C^2 floats): AccumulateGrad keeps the returned views -- and with them their
+        # storage -- alive as long as .grad lives; sharing a slab with the 3 N C floats of fp32 scratch pinned ~77 MB per stage-0 Block
+        # (ADVICE r3).  The fp32 scratch gradients (and dx0 of an fp32 stream) and the 16-bit ones live in two transient slabs.
+        slabs = {E["SLAB_SAVED16"]: buf16, E["SLAB_SAVED32"]: buf32}
+        for k, slab_dt in (("SLAB_PGRAD", torch.float32), ("SLAB_SCRATCH32", torch.float32), ("SLAB_SCRATCH16", dt)):
+            slabs[E[k]] = _blk_alloc(plan["bytes"][E[k]], slab_dt, dev)
+        pslab, nslab = _blk_slab_args(E, slabs)
         if plan["ws"] is None:
             plan["ws"] = int(ops.lib().ptc_ptv3_block_workspace_bytes(n, npad, c, heads))
         nbytes = plan["ws"]
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ops.lib().ptc_ptv3_block_bwd(iv, fv, pin, psv, pg, ws.data_ptr(), nbytes, ops.stream_ptr())
-        dx0 = (gscr if x0.dtype == torch.float32 else sbuf)[plan["gx0"]:plan["gx0"] + n * c].view(n, c)
-        dxc = sbuf[plan["gxc"]:plan["gxc"] + n * c].view(n, c)
+        ops.lib().ptc_ptv3_block_bwd(iv, fv, pin, pslab, nslab, x3.data_ptr(), ws.data_ptr(), nbytes, ops.stream_ptr())
+
+        def cut(name, shape):      # the slot as a view of its slab (G_X0 lies in the slab of x0's dtype)
+            slab, lo, hi = plan["cut"][name]
+            t = slabs[slab]
+            return t[lo // t.element_size():hi // t.element_size()].view(shape)
+
+        dx0, dxc = cut("G_X0", x0.shape), cut("G_XC", x0.shape)
         grads = []
         for k, present, pdt, shp in zip(_BLK_PARAMS, ctx.present, ctx.param_dtypes, ctx.param_shapes):
             if not present:
                 grads.append(None)
                 continue
-            off, cnt = plan["gparam"][k]
-            g = gbuf[off:off + cnt].view(shp)
+            g = cut("G_" + k, shp)
             grads.append(g if pdt == torch.float32 else g.to(pdt))
         return (dx0, dxc, None, None, None, *grads)
 

@@ -325,7 +325,9 @@ def test_derived_signatures_match_a_pinned_sample():
         "ptc_sort_keys_workspace_bytes": (sz, [i64, ci]),
         "ptc_hash_table_size": (i64, [i64]),
         "ptc_ptv3_block_abi": (ci, []),
-        "ptc_ptv3_block_fwd": (ci, [vp, vp, vp, vp, vp, sz, vp]),                    # const void* const*, void* const*
+        "ptc_ptv3_block_fwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),        # const void* const*, void* const*, const int64_t*
+        "ptc_ptv3_block_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "ptc_ptv3_block_layout": (sz, [vp, vp, vp, vp, vp]),                         # a query that fills arrays: no stream, not a status
         "ptc_voxel_keys": (ci, [vp, i64, f64, vp, vp, vp, vp]),
         "ptc_attn_varlen_dropout_fwd": (ci, [vp, vp, i64, i64, ci, ci, f32, ci, f32, u64, vp, vp, vp]),
         "ptc_msc_csc_nce_fwd": (ci, [vp, i64, vp, i64, vp, vp, vp, ci, vp, i64, ci, f32, f32, f32, ci] + [vp] * 14 + [vp, sz, vp]),
@@ -333,7 +335,7 @@ def test_derived_signatures_match_a_pinned_sample():
     table = _lib.HEADER.signatures
     for name, want in pinned.items():
         assert tuple(table[name][:2]) == want, name
-    assert len(table) == 178 == len(re.findall(r"\bptc_\w+\s*\(", _header_without_comments()))
+    assert len(table) == 179 == len(re.findall(r"\bptc_\w+\s*\(", _header_without_comments()))
     assert _lib.exported_symbols() == sorted(table) and _lib._SIGNATURES == {name: tuple(v[:2]) for name, v in table.items()}
 
 
@@ -386,10 +388,11 @@ def test_constants_come_from_the_header_with_their_values():
     assert _lib.ORDER_CODES == {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
     assert _lib.HEADER.enums["ptc_status"] == {"PTC_OK": 0, "PTC_EINVAL": -1, "PTC_EUNSUPPORTED": -2, "PTC_EHIP": -3, "PTC_EWORKSPACE": -4}
     E = _lib.block_enums()
-    assert len(E) == 110 and all(not k.startswith("PTC_") for k in E)
-    assert {k: E[k] for k in ("ABI", "I_COUNT", "F_COUNT", "P_COUNT", "O_COUNT", "GS_COUNT")} == \
-        {"ABI": 3, "I_COUNT": 11, "F_COUNT": 4, "P_COUNT": 40, "O_COUNT": 18, "GS_COUNT": 31}
+    assert len(E) == 117 and all(not k.startswith("PTC_") for k in E)
+    assert {k: E[k] for k in ("ABI", "I_COUNT", "F_COUNT", "P_COUNT", "O_COUNT", "GS_COUNT", "SLAB_COUNT", "SLOT_COUNT")} == \
+        {"ABI": 4, "I_COUNT": 11, "F_COUNT": 4, "P_COUNT": 40, "O_COUNT": 18, "GS_COUNT": 31, "SLAB_COUNT": 5, "SLOT_COUNT": 49}
     assert (E["I_ABI"], E["I_DTYPE"], E["P_W_QKV"], E["O_LSE"], E["G_W_FC2"], E["S_DCONV"]) == (0, 6, 22, 8, 18, 30)
+    assert [E["SLAB_" + k] for k in ("SAVED16", "SAVED32", "PGRAD", "SCRATCH32", "SCRATCH16")] == [0, 1, 2, 3, 4]
 
 
 def test_host_probe_binds_every_probe_function():
@@ -437,9 +440,11 @@ def test_argument_validation_returns_error_codes():
     assert fwd_blk(None, need) == -4 and b"workspace" in L.ptc_last_error()
     assert fwd_blk(p, need - 1) == -4 and b"workspace" in L.ptc_last_error()
     assert fwd_blk(p + 8, need) == -1 and b"aligned" in L.ptc_last_error()
-    # the Block executor's forward: the same workspace, and tables of the previous ABI revision are refused
+    # the Block executor: the forward's workspace as above; the slabs are checked against the library's own layout -- any one of them one
+    # byte short is PTC_EWORKSPACE and named, a misaligned base PTC_EINVAL -- and tables of the previous ABI revision are refused.  All of
+    # it before any launch: the pointers are dummies
     E = _lib.block_enums()
-    assert E["ABI"] == 3 and L.ptc_ptv3_block_abi() == 3
+    assert E["ABI"] == 4 and L.ptc_ptv3_block_abi() == 4
     assert L.ptc_ptv3_block_fwd_workspace_bytes(2048, 128) == L.ptc_spconv_fwd_blk_workspace_bytes(2048, 27, 128, 128) > 0
     assert L.ptc_ptv3_block_fwd_workspace_bytes(2048, 64) == 0
     iv = (ctypes.c_int64 * E["I_COUNT"])()
@@ -447,10 +452,31 @@ def test_argument_validation_returns_error_codes():
     iv[E["I_DTYPE"]], iv[E["I_A_DTYPE"]], iv[E["I_PATCH"]], iv[E["I_BLK_BM"]], iv[E["I_BLK_HCAP"]] = 2, 0, 1024, 128, 416
     fv = (ctypes.c_float * E["F_COUNT"])()
     pin = (ctypes.c_void_p * E["P_COUNT"])()
-    pout = (ctypes.c_void_p * E["O_COUNT"])()
-    assert L.ptc_ptv3_block_fwd(iv, fv, pin, pout, None, 0, None) == -4 and b"workspace" in L.ptc_last_error()
-    iv[E["I_ABI"]] = 2
-    assert L.ptc_ptv3_block_fwd(iv, fv, pin, pout, None, 0, None) == -1 and b"ABI" in L.ptc_last_error()
+    totals = (ctypes.c_int64 * E["SLAB_COUNT"])()
+    slots = [(ctypes.c_int64 * E["SLOT_COUNT"])() for _ in range(3)]
+    assert L.ptc_ptv3_block_layout(iv, totals, *slots) == E["SLOT_COUNT"] and all(t > 0 and t % 256 == 0 for t in totals)
+    names = ("saved16", "saved32", "param_grad", "scratch32", "scratch16")
+    ws_fwd, ws_bwd = L.ptc_ptv3_block_fwd_workspace_bytes(2048, 128), L.ptc_ptv3_block_workspace_bytes(2048, 2048, 128, 8)
+
+    def block_call(direction, short=None, misaligned=None, ws=True):
+        bases = (ctypes.c_void_p * E["SLAB_COUNT"])(*[p + (8 if i == misaligned else 0) for i in range(E["SLAB_COUNT"])])
+        sizes = (ctypes.c_int64 * E["SLAB_COUNT"])(*[t - (i == short) for i, t in enumerate(totals)])
+        if direction == "fwd":
+            return L.ptc_ptv3_block_fwd(iv, fv, pin, bases, sizes, p, p, p if ws else None, ws_fwd if ws else 0, None)
+        return L.ptc_ptv3_block_bwd(iv, fv, pin, bases, sizes, p, p, ws_bwd if ws else 0, None)
+
+    assert block_call("fwd", ws=False) == -4 and b"workspace" in L.ptc_last_error()
+    assert block_call("bwd", ws=False) == -4 and b"workspace" in L.ptc_last_error()
+    for i, name in enumerate(names):
+        assert block_call("bwd", short=i) == -4 and b"workspace" in L.ptc_last_error() and name.encode() in L.ptc_last_error(), name
+        assert block_call("bwd", misaligned=i) == -1 and b"aligned" in L.ptc_last_error() and name.encode() in L.ptc_last_error(), name
+        if i <= E["SLAB_SAVED32"]:        # the forward reads the two saved slabs only
+            assert block_call("fwd", short=i) == -4 and b"workspace" in L.ptc_last_error() and name.encode() in L.ptc_last_error(), name
+            assert block_call("fwd", misaligned=i) == -1 and b"aligned" in L.ptc_last_error() and name.encode() in L.ptc_last_error(), name
+    iv[E["I_ABI"]] = 3
+    assert block_call("fwd") == -1 and b"ABI" in L.ptc_last_error()
+    assert block_call("bwd") == -1 and b"ABI" in L.ptc_last_error()
+    assert L.ptc_ptv3_block_layout(iv, totals, *slots) == 0 and b"ABI" in L.ptc_last_error()
     # the same calls on the checked handle: PtcoreError, .code the status, the text check() gives ("<name> failed with code <rc>: <msg>")
     C = _lib.lib()
     assert C is not L and C.ptc_serialize_encode is not L.ptc_serialize_encode
@@ -470,7 +496,7 @@ def test_argument_validation_returns_error_codes():
     # predicates and size queries return their values on both handles and never raise
     for H in (L, C):
         assert H.ptc_layer_norm_supported(7) == 0 and H.ptc_layer_norm_supported(64) == 1
-        assert H.ptc_spconv_fwd_blk_workspace_bytes(9000, 27, 128, 96) == need and H.ptc_ptv3_block_abi() == 3
+        assert H.ptc_spconv_fwd_blk_workspace_bytes(9000, 27, 128, 96) == need and H.ptc_ptv3_block_abi() == 4
         assert getattr(H.ptc_layer_norm_supported, "errcheck", None) is None
 
 
